@@ -27,12 +27,17 @@ children with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 set --
 relays rank 0's single JSON line and exits with the first failing rank's code.
 It refuses to run (exit 2) when fewer than N GPUs are visible.
 
+A plain run sets up, warms up, times the K steps and prints the line (``value``,
+``ms_per_step``); ``--dump-outputs DIR`` also writes the last timed step's batch
+as ``DIR/batch.npy`` (float32).  Every other block below runs only with ``--full``.
+
 Blocks in the one JSON line (all timed between a barrier + synchronize on both
 sides, max over ranks, whole-job records):
   * ``value``: the driver's K steps (after W warm-up steps);
-  * ``steady_state``: ``--steady-steps`` more steps of the same loader (default
-    50 000: >= 0.25 s at the measured rate; the workers' prefilled slots are a
-    fraction of a percent of it), with per-rank rates and the lockstep's cost;
+  * ``steady_state`` (this block and the following ones: ``--full``):
+    ``--steady-steps`` more steps of the same loader (default 50 000: >= 0.25 s
+    at the measured rate; the workers' prefilled slots are a fraction of a percent of it),
+    with per-rank rates and the lockstep's cost;
   * ``steady_dma``: a second loader (own consumer group, same topic from the
     earliest offset) with ``h2d="dma"``: the partition logs are copied into HBM
     by hipMemcpyAsync on a side stream (SDMA) and decoded there -- the config-2
@@ -69,6 +74,15 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=200)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the steady-state block, the secondary steady blocks "
+                         "(--extra-blocks), the Kafka-protocol bridge blocks and the single-GPU configuration "
+                         "blocks (--config-blocks); without it only the headline's steps are run and timed")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the batch the last timed step delivered as DIR/batch.npy "
+                         "(float32; DIR/batch_rank<r>.npy per rank at N > 1).  Batches are then delivered in strict "
+                         "worker round-robin order (as with --in-order), so the same arguments give the same batch "
+                         "on every run")
     ap.add_argument("--batch-size", type=int, default=256)
     ap.add_argument("--dim", type=int, default=256, help="float32 elements per record")
     ap.add_argument("--workers", type=int, default=4)
@@ -747,6 +761,25 @@ def _config_block(R: "Rank", args, m_import, name: str, dev: str, on_gpu: bool):
     return name, res
 
 
+DUMP_LIMIT_BYTES = 60 << 20  # under 64 MB with the .npy header
+
+
+def dump_outputs(R: "Rank", out_dir: str, batch) -> dict:
+    """--dump-outputs: the batch the last timed step handed to the caller, as float32 ``.npy``.
+    A batch above DUMP_LIMIT_BYTES is cut to a fixed, seeded sample of its rows (sorted)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    a = batch.detach().float().cpu().numpy()
+    rows = a.shape[0]
+    keep = DUMP_LIMIT_BYTES // max(1, a[0].nbytes) if rows else 0
+    if rows > keep:
+        a = a[np.sort(np.random.RandomState(0).choice(rows, size=keep, replace=False))]
+    name = "batch.npy" if R.world == 1 else f"batch_rank{R.rank}.npy"
+    np.save(os.path.join(out_dir, name), np.ascontiguousarray(a, dtype=np.float32))
+    return {"file": name, "shape": list(a.shape), "rows_of_batch": rows}
+
+
 def run_rank(args) -> int:
     R = Rank(args)
     torch, dist = R.torch, R.dist
@@ -781,8 +814,6 @@ def run_rank(args) -> int:
     url = f"shm://tkbench-{tag}"
     n_parts = args.partitions_per_gpu * world
     B = args.batch_size
-    broker = SyntheticBroker.create(url, log_capacity=1 << 34, index_capacity=1 << 22)
-    broker.create_topic("bench", n_parts)
     # backlog per owned partition: every batch the timed loop and the warm-up consume, plus what the
     # workers prefetch into their ring slots, with headroom (the secondary blocks re-read it from the
     # earliest offset under consumer groups of their own)
@@ -802,6 +833,10 @@ def run_rank(args) -> int:
     extra_warm = max(50, args.warmup)
 
     bsteps = args.bridge_steps if args.bridge_steps is not None else (8000 if device.type == "cuda" else 20)
+    if not args.full:
+        # a plain run times the headline only: no steady, secondary, bridge or configuration blocks,
+        # and a backlog sized for the warm-up and the timed steps
+        steady, extra, bsteps, args.config_blocks = 0, [], 0, ""
 
     def backlog(steady_n, extra_n):
         # every block re-reads the topic from the earliest offset under a group of its own: the
@@ -823,6 +858,12 @@ def run_rank(args) -> int:
         if steady < 2000:
             print(f"[bench] rank {rank}: not enough memory for the backlog ({preflight}): refusing", file=sys.stderr)
             return 2
+    # a partition's log and batch index hold its whole backlog: the usual capacities, or what a long
+    # --steps run needs (the log files are sparse, only the filled part takes memory)
+    broker = SyntheticBroker.create(
+        url, log_capacity=max(1 << 34, -(-int(per_part * record_bytes(args) * 1.1) >> 20) << 20),
+        index_capacity=max(1 << 22, 2 * per_part // max(1, args.records_per_batch)))
+    broker.create_topic("bench", n_parts)
     t_fill = time.perf_counter()
     broker.fill("bench", per_part, "fixed_f32", size=args.dim, partitions=mine,
                 records_per_batch=args.records_per_batch, threads=min(16, len(mine)), keyed=True)
@@ -835,7 +876,7 @@ def run_rank(args) -> int:
         return DeviceLoader(
             ds.placeholder(), B, num_workers=args.workers, device=device, dtype=dtype,
             slots_per_worker=args.slots_per_worker, prefetch=args.prefetch, rank=rank, world_size=world,
-            in_order=args.in_order, h2d=h2d, copy_streams=args.copy_streams,
+            in_order=args.in_order or bool(args.dump_outputs), h2d=h2d, copy_streams=args.copy_streams,
             **({"lockstep_depth": args.lockstep_depth} if args.lockstep_depth is not None else {}),
             **({"lockstep_commit_every": args.lockstep_commit_every} if args.lockstep_commit_every is not None
                else {}),
@@ -875,6 +916,7 @@ def run_rank(args) -> int:
     elapsed, total_rows, stats = head["el"], head["rows"], head["stats"]
     value = total_rows / elapsed
     h2d_desc, decode_desc = describe(loader)
+    dumped = dump_outputs(R, args.dump_outputs, head["last"]) if args.dump_outputs else None
 
     if args.window_trace > 0 and rank == 0:
         print(json.dumps({"window_trace": window_trace(R, it, args.steps, args.window_trace, loader)}), file=sys.stderr)
@@ -1112,6 +1154,9 @@ def run_rank(args) -> int:
             "prefilled_slots_at_t0": head["occ"]["prefilled"],
             "ring_slots": head["occ"]["n_slots"],
             "fill_s": round(t_fill, 2),
+            "full": args.full,
+            "delivery": "in order (worker round-robin)" if args.in_order or args.dump_outputs else "first ready",
+            "outputs": dumped,
             "steady_state": steady_out,
             **extra_out,
             "bridge": bridge_out,

@@ -37,7 +37,7 @@ def _torchrun(nproc, script, *args, timeout=240, env=None):
 
 
 def test_bench_two_ranks_gloo_cpu():
-    r = _torchrun(2, "bench.py", "--gpus", "2", "--steps", "30", "--warmup", "5", "--device", "cpu",
+    r = _torchrun(2, "bench.py", "--gpus", "2", "--full", "--steps", "30", "--warmup", "5", "--device", "cpu",
                   "--steady-steps", "60", "--workers", "2", "--partitions-per-gpu", "4", "--bridge-steps", "8")
     assert r.returncode == 0, r.stdout[-3000:]
     lines = [json.loads(x) for x in r.stdout.splitlines() if x.startswith('{"metric"')]
@@ -51,7 +51,7 @@ def test_bench_two_ranks_gloo_cpu():
 def test_bench_late_block_watchdog_still_prints_the_line():
     """A late (RCCL) block that hangs on every rank: each rank's watchdog gives up after
     TK_BENCH_LATE_TIMEOUT, rank 0 prints the one line with the block marked, and the job exits 0."""
-    r = _torchrun(2, "bench.py", "--gpus", "2", "--steps", "20", "--warmup", "5", "--device", "cpu",
+    r = _torchrun(2, "bench.py", "--gpus", "2", "--full", "--steps", "20", "--warmup", "5", "--device", "cpu",
                   "--steady-steps", "40", "--extra-blocks", "", "--workers", "1", "--partitions-per-gpu", "2",
                   "--bridge-steps", "0", env={"TK_BENCH_TEST_LATE_HANG": "1", "TK_BENCH_LATE_TIMEOUT": "8"})
     assert r.returncode == 0, r.stdout[-3000:]
@@ -66,7 +66,7 @@ def test_bench_failed_block_is_reported_and_the_run_goes_on():
     """One rank's secondary block fails (session r06_s18: a device CRC verdict in the four-rank dma
     block): the others leave the lockstepped block at once, the failure is reported under the
     block's key, and the later blocks and the line still run."""
-    r = _torchrun(2, "bench.py", "--gpus", "2", "--steps", "20", "--warmup", "5", "--device", "cpu",
+    r = _torchrun(2, "bench.py", "--gpus", "2", "--full", "--steps", "20", "--warmup", "5", "--device", "cpu",
                   "--steady-steps", "40", "--extra-blocks", "label,f32", "--extra-steps", "4000", "--workers", "1",
                   "--partitions-per-gpu", "2", "--bridge-steps", "8", "--bridge-codecs", "",
                   env={"TK_BENCH_TEST_FAIL_BLOCK": "label"})
@@ -88,7 +88,7 @@ def _bench(*args, timeout=240):
 
 def test_bench_self_launches_n_ranks_without_torchrun():
     """The driver's plain `python bench.py --gpus N` runs N ranks (never one rank silently)."""
-    r = _bench("--gpus", "2", "--device", "cpu", "--steps", "30", "--warmup", "5", "--steady-steps", "60",
+    r = _bench("--gpus", "2", "--full", "--device", "cpu", "--steps", "30", "--warmup", "5", "--steady-steps", "60",
                "--extra-blocks", "f32", "--extra-steps", "40", "--workers", "2", "--bridge-steps", "8")
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [json.loads(x) for x in r.stdout.splitlines() if x.startswith('{"metric"')]
@@ -105,6 +105,34 @@ def test_bench_self_launches_n_ranks_without_torchrun():
     br = out["bridge"]
     assert br["async"]["steps"] == 8 and br["sync"]["steps"] == 2 and len(br["sync"]["per_rank_records_per_s"]) == 2
     assert br["async"]["bridge_errors"] == 0 and br["sync"]["sync_commits"] >= 1
+
+
+def test_bench_plain_run_times_the_headline_alone_and_dumps_its_last_batch(tmp_path):
+    """Without --full only the headline's steps run; --dump-outputs writes the batch of the last timed
+    step as float32, the same batch on every run, holding what the broker's generator produced."""
+    import numpy as np
+
+    from conftest import synth_f32
+
+    dumps = []
+    for d in ("a", "b"):
+        r = _bench("--gpus", "1", "--device", "cpu", "--steps", "12", "--warmup", "3", "--batch-size", "64",
+                   "--dim", "16", "--dtype", "f32", "--workers", "2", "--dump-outputs", str(tmp_path / d))
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [json.loads(x) for x in r.stdout.splitlines() if x.startswith('{"metric"')]
+        assert len(lines) == 1, r.stdout[-3000:]
+        out = lines[0]
+        assert out["full"] is False and out["steps"] == 12 and out["value"] > 0
+        assert out["steady_state"] is None and out["bridge"] is None
+        others = [k for k in out if k.startswith(("steady_", "config", "train", "process"))]
+        assert sorted(others) == ["config", "steady_state"], others  # the run's settings; None (above)
+        assert abs(out["ms_per_step"] - out["timed_region_s"] / 12 * 1000) < 1e-3
+        assert out["outputs"] == {"file": "batch.npy", "shape": [64, 16], "rows_of_batch": 64}
+        dumps.append(np.load(tmp_path / d / "batch.npy"))
+    a, b = dumps
+    assert a.dtype == np.float32 and a.shape == (64, 16) and np.array_equal(a, b)
+    want = np.array([[synth_f32(int(row[1]), int(row[0]), j) for j in range(16)] for row in a], dtype=np.float32)
+    assert np.array_equal(a, want)
 
 
 def test_bench_refuses_more_ranks_than_visible_gpus():
@@ -139,7 +167,7 @@ def test_native_lockstep_two_ranks_one_gpu():
 def test_bench_eight_ranks_on_cpu_without_torchrun():
     """The driver's N = 8 command line (`python bench.py --gpus 8`, no torchrun) rehearsed on the CPU
     over gloo: 8 self-launched ranks, 64 partitions, every rank's rate reported, one JSON line."""
-    r = _bench("--gpus", "8", "--device", "cpu", "--workers", "1", "--steps", "20", "--warmup", "5",
+    r = _bench("--gpus", "8", "--full", "--device", "cpu", "--workers", "1", "--steps", "20", "--warmup", "5",
                "--steady-steps", "200", "--extra-blocks", "", "--bridge-steps", "0", "--config-blocks", "",
                timeout=400)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -164,8 +192,9 @@ def test_bench_launcher_parent_never_initialises_hip(tmp_path):
     e.pop("WORLD_SIZE", None)
     e["TK_BENCH_PARENT_REPORT"] = str(rep)
     e["PYTHONPATH"] = ROOT + os.pathsep + e.get("PYTHONPATH", "")
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--self-launch", "--steps", "20", "--warmup", "5",
-                        "--steady-steps", "500", "--extra-blocks", "", "--bridge-steps", "0", "--config-blocks", ""],
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--full", "--self-launch", "--steps", "20",
+                        "--warmup", "5", "--steady-steps", "500", "--extra-blocks", "", "--bridge-steps", "0",
+                        "--config-blocks", ""],
                        cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=240, env=e)
     assert r.returncode == 0, r.stderr[-3000:]
     parent = json.load(open(rep))
