@@ -88,13 +88,27 @@ int main(int argc, char** argv) {
   tkh::HipQueue f(0);
   std::atomic<bool> skipped_ran{false};
   uint64_t s_bad = 0, s_after = 0;
-  for (int tries = 0; tries < 100 && s_bad == 0; ++tries) {
-    // queue behind a slow call, so the failing call and the one after it run on the thread
-    f.submit([] { std::this_thread::sleep_for(std::chrono::milliseconds(5)); });
-    s_bad = f.submit([] { throw std::runtime_error("launch failed"); });
+  std::atomic<bool> go{false};
+  const std::thread::id main_id = std::this_thread::get_id();
+  const auto give_up = std::chrono::steady_clock::now() + std::chrono::seconds(20);
+  while (s_bad == 0 && std::chrono::steady_clock::now() < give_up) {
+    // queue behind a call that holds the thread until `go`, so the failing call and the one after
+    // it run on the thread whatever the scheduling (a call that merely slept could be over, and
+    // the thread asleep again, before the next submit: the failing call then ran inline here and
+    // threw out of submit)
+    const uint64_t s_gate = f.submit([&go, main_id] {
+      if (std::this_thread::get_id() == main_id) return;  // ran inline: the thread was asleep
+      while (!go.load(std::memory_order_acquire)) std::this_thread::sleep_for(std::chrono::microseconds(50));
+    });
+    if (s_gate == 0) {  // the inline call woke the thread: ask again until it is seen awake
+      std::this_thread::yield();
+      continue;
+    }
+    s_bad = f.submit([] { throw std::runtime_error("launch failed"); });  // queued: the gate has not run
   }
   CHECK(s_bad != 0);
   s_after = f.submit([&skipped_ran] { skipped_ran.store(true); });
+  go.store(true, std::memory_order_release);
   auto throws = [](auto&& fn) {
     try {
       fn();
@@ -114,10 +128,19 @@ int main(int argc, char** argv) {
   {
     tkh::HipQueue g(0);
     std::atomic<int> ok{0};
-    for (int i = 0; i < 100; ++i) g.submit([&ok] { ok.fetch_add(1); });
+    // at least 100 calls, and on until one was queued (calls made while the thread sleeps run inline
+    // and get no number: on a busy machine the first hundred can all be of that kind)
+    int calls = 0;
+    uint64_t last = 0;
+    while (calls < 100 || (last == 0 && std::chrono::steady_clock::now() < give_up)) {
+      const uint64_t s = g.submit([&ok] { ok.fetch_add(1); });
+      if (s) last = s;
+      if (++calls >= 100) std::this_thread::yield();
+    }
     g.drain();
-    CHECK(ok.load() == 100);
-    CHECK(g.ran(1));
+    CHECK(ok.load() == calls);
+    CHECK(last != 0);
+    CHECK(g.ran(1) && g.ran(last));
   }
   std::printf("hip_queue_test: ok (%d ordered calls, inline path, failure report, failed-queue answers, "
               "per-loader queues)\n", n);

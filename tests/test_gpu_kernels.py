@@ -168,6 +168,169 @@ def test_extension_is_native():
     assert "gfx950" in info["gcn_arch"], info
 
 
+# ----------------------------------------------------------------------------- known contents, plain-torch expected
+# (tests/helpers/known_records.py: nothing below calls reference_fixed / reference_varlen)
+from helpers import known_records as kr  # noqa: E402
+
+INT_SRCS = [torch.int32, torch.int64]
+
+
+def _pid(v):
+    """Readable test ids: float32 instead of src_dt0."""
+    return str(v).replace("torch.", "") if isinstance(v, torch.dtype) else None
+
+
+@pytest.mark.parametrize("row", [8, 13, 264], ids=_pid)
+@pytest.mark.parametrize("dst", FLOATS, ids=_pid)
+@pytest.mark.parametrize("src_dt", [torch.float32, torch.bfloat16, torch.float16, torch.uint8, torch.int8,
+                                    torch.int32], ids=_pid)
+def test_fixed_normalize_matrix(src_dt, dst, row):
+    """Per-feature normalisation from every source type (float inputs with denormals, infinities and
+    NaN) to every float type; row 8 / 264: the vector kernel, row 13: fixed_scalar_kernel<.., true>."""
+    from torchkafka_amd.ops.collate import collate_fixed
+
+    src = kr.known_rows(src_dt, (row,), 37, seed=row + 7)
+    mean, std = kr.norm_vectors(row, seed=row)
+    want = kr.expected_fixed(src, dst, mean, std)
+    out = collate_fixed(src.cuda(), dst, normalize=(mean, std))
+    kr.assert_same(out, want)
+    if dst == torch.float32:
+        kr.assert_within_f32_bound(want, src, mean, std, "expected")
+        kr.assert_within_f32_bound(out, src, mean, std)
+
+
+@pytest.mark.parametrize("norm", [False, True], ids=_pid)
+@pytest.mark.parametrize("row", [8, 264], ids=_pid)
+@pytest.mark.parametrize("src_dt,skip,rem", [(torch.float32, 1, 4), (torch.uint8, 3, 3)], ids=_pid)
+def test_fixed_unaligned_source_takes_the_scalar_fallback(src_dt, skip, rem, row, norm):
+    """A source that is not 16-byte aligned (a view one f32 / three bytes into a device buffer):
+    launch_fixed_t must leave the vector kernel, with and without normalisation."""
+    from torchkafka_amd.ops.collate import collate_fixed
+
+    src = kr.known_rows(src_dt, (row,), 37, seed=row + skip)
+    buf = torch.zeros(skip + src.numel() + 16, dtype=src_dt, device="cuda")
+    view = buf[skip:skip + src.numel()].view(37, row)
+    view.copy_(src)
+    assert view.is_contiguous() and view.data_ptr() % 16 == rem
+    mean, std = kr.norm_vectors(row, seed=3)
+    for dst in (torch.float32, torch.bfloat16):
+        out = collate_fixed(view, dst, normalize=(mean, std) if norm else None)
+        kr.assert_same(out, kr.expected_fixed(src, dst, *((mean, std) if norm else ())))
+
+
+@pytest.mark.parametrize("row", [8, 13], ids=_pid)
+@pytest.mark.parametrize("dst", FLOATS, ids=_pid)
+@pytest.mark.parametrize("src_dt", INT_SRCS, ids=_pid)
+def test_fixed_full_range_integers_to_floats(src_dt, dst, row):
+    """min / max, +-(2^24 + 1), +-(2^24 + 3), values past every float type's range: rounding above
+    2^24, overflow to inf in f16, NaN saturation in fp8 -- all as Tensor.to."""
+    from torchkafka_amd.ops.collate import collate_fixed
+
+    src = kr.known_rows(src_dt, (row,), 64, seed=row)
+    kr.assert_same(collate_fixed(src.cuda(), dst), src.to(dst))
+
+
+@pytest.mark.parametrize("row", [8, 13], ids=_pid)
+@pytest.mark.parametrize("src_dt", [torch.int64, torch.uint8], ids=_pid)
+def test_fixed_full_range_integers_to_int32(src_dt, row):
+    from torchkafka_amd.ops.collate import collate_fixed
+
+    src = kr.known_rows(src_dt, (row,), 64, seed=row + 1)
+    kr.assert_same(collate_fixed(src.cuda(), torch.int32), src.to(torch.int32))  # int64 wraps
+
+
+_TIES = {}
+
+
+def _tie_set(name: str) -> torch.Tensor:
+    """The tie sweep of one format (built once), padded with zeros to a multiple of 8 * 13."""
+    if name not in _TIES:
+        x = {"bf16": kr.bf16_tie_values, "f16": kr.f16_tie_values, "e4m3": kr.e4m3_tie_values}[name]()
+        pad = -x.numel() % 104
+        _TIES[name] = torch.cat([x, torch.zeros(pad)])
+    return _TIES[name]
+
+
+@pytest.mark.parametrize("dst", FLOATS, ids=_pid)
+@pytest.mark.parametrize("name", ["bf16", "f16", "e4m3"], ids=_pid)
+def test_rounding_tie_sweep(name, dst):
+    """Tie and boundary bit patterns of bf16, f16 and e4m3fn (not decimal constants) through the vector
+    kernel (row 8), the scalar kernel (row 13) and the var-len kernel (one row), against Tensor.to."""
+    from torchkafka_amd.ops.collate import collate_fixed, collate_varlen
+
+    x = _tie_set(name)
+    want = x.to(dst)
+    xd = x.cuda()
+    for row in (8, 13):
+        kr.assert_same(collate_fixed(xd.view(-1, row), dst), want.view(-1, row), f"row {row}")
+    offs = torch.tensor([0, x.numel()], dtype=torch.int32)
+    out, ln = collate_varlen(offs.cuda(), xd, dst, L=x.numel())
+    kr.assert_same(out, want.view(1, -1), "varlen")
+    assert ln.tolist() == [x.numel()]
+
+
+def _csr(lens):
+    offs = torch.zeros(len(lens) + 1, dtype=torch.int32)
+    offs[1:] = torch.tensor(lens, dtype=torch.int64).cumsum(0).to(torch.int32)
+    return offs
+
+
+def _check_varlen(offs, vals, dst, L, pad):
+    from torchkafka_amd.ops.collate import collate_varlen
+
+    rows = [vals[int(offs[i]):int(offs[i + 1])] for i in range(offs.numel() - 1)]
+    w_out, w_len, w_mask = kr.expected_varlen(rows, dst, L, pad)
+    out, ln, mask = collate_varlen(offs.cuda(), vals.cuda(), dst, L=L, pad_value=pad, return_mask=True)
+    kr.assert_same(out, w_out)
+    assert torch.equal(ln.cpu(), w_len) and torch.equal(mask.cpu(), w_mask)
+
+
+@pytest.mark.parametrize("src_dt,dst", [(torch.bfloat16, torch.float32), (torch.float32, torch.bfloat16)], ids=_pid)
+def test_varlen_offsets_not_starting_at_zero(src_dt, dst):
+    """offsets[k:] of a longer CSR with the full values tensor: offsets[0] > 0, for the LDS-staged
+    kernel (2-byte source: the first row starts at an odd dword) and the direct one (4-byte)."""
+    lens = [5, 3, 0, 2049, 17, 1, 300, 8]
+    offs = _csr(lens)
+    vals = kr.known_values(src_dt, int(offs[-1]), seed=21)
+    for k in (1, 2, 4):
+        assert int(offs[k]) > 0
+        _check_varlen(offs[k:], vals, dst, max(lens[k:]) + 3, 0.5)
+        # as a view of the device CSR too: offsets.data_ptr() then points into the longer tensor
+        from torchkafka_amd.ops.collate import collate_varlen
+
+        rows = [vals[int(offs[i]):int(offs[i + 1])] for i in range(k, len(lens))]
+        out, ln = collate_varlen(offs.cuda()[k:], vals.cuda(), dst, L=max(lens[k:]))
+        w_out, w_len, _ = kr.expected_varlen(rows, dst, max(lens[k:]))
+        kr.assert_same(out, w_out)
+        assert torch.equal(ln.cpu(), w_len)
+
+
+@pytest.mark.parametrize("src_dt,dst,pad", [
+    (torch.float32, torch.bfloat16, 0.1), (torch.float32, torch.float8_e4m3fn, 0.1),
+    (torch.float16, torch.float8_e4m3fn, 0.1), (torch.int64, torch.int32, -1), (torch.uint8, torch.int32, -1)],
+    ids=_pid)
+def test_varlen_pad_value_is_rounded_like_the_values(src_dt, dst, pad):
+    lens = [0, 1, 7, 8, 9, 40]
+    offs = _csr(lens)
+    _check_varlen(offs, kr.known_values(src_dt, int(offs[-1]), seed=4), dst, 43, pad)
+
+
+@pytest.mark.parametrize("src_dt,dst", [(torch.float32, torch.float16), (torch.uint8, torch.float32),
+                                        (torch.int64, torch.int64)], ids=_pid)
+@pytest.mark.parametrize("lens,L", [
+    ([9, 12, 30, 2050], 5),      # L shorter than every row
+    ([9, 12, 30, 2050], 1),      # L = 1
+    ([0, 0, 0], 5),              # all rows empty
+    ([3, 6501, 0], 6501),        # one row over more than three 2048-element chunks, L % 8 != 0
+    ([3, 6501, 0], 6499),        # ... cut inside its last chunk
+], ids=_pid)
+def test_varlen_width_edges(src_dt, dst, lens, L):
+    offs = _csr(lens)
+    n = int(offs[-1])
+    vals = kr.known_values(src_dt, max(n, 1), seed=L)[:n]
+    _check_varlen(offs, vals, dst, L, 2)
+
+
 # ----------------------------------------------------------------------------- property-based (hypothesis)
 from hypothesis import HealthCheck, given, settings  # noqa: E402
 from hypothesis import strategies as st  # noqa: E402

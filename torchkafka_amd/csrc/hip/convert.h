@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "dtypes.h"
 
@@ -23,7 +24,15 @@ template <typename S, typename D>
 struct Conv<S, D, false> {  // float destination
   __device__ __forceinline__ static D apply(S s, float shift, float scale, bool affine) {
     float x = to_f32<S>(s);
-    if (affine) x = (x - shift) * scale;
+    if (affine) {
+      x = (x - shift) * scale;
+      // f16: the product must be rounded to f32 before it is rounded to f16, as Tensor.to rounds
+      // the f32 tensor.  Left alone the compiler fuses the multiply and the conversion into one
+      // v_fma_mixlo_f16, which rounds the exact product once: off by one f16 ulp where the two
+      // roundings disagree (and only in the kernels where it chose to fuse).  The empty asm makes
+      // the f32 value opaque between the two; it emits no instruction.
+      if constexpr (std::is_same<D, _Float16>::value) asm("" : "+v"(x));
+    }
     return Store<D>::cvt(x);
   }
 };
