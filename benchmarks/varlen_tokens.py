@@ -9,7 +9,12 @@ varlen_span_kernel reads the values straight from the pinned broker logs (CRC32C
 device); ``--decode host``: the workers CRC-check and pack CSR into the ring, the varlen collate
 kernel pads.
 
-Usage: python benchmarks/varlen_tokens.py [--steps K] [--decode device|host]
+``--layout packed`` delivers each batch in the packed (cu_seqlens) layout instead: flat values with the
+rows back to back, made from the padded batch by one more launch (pack.hip).  The JSON line carries
+``padding_fraction``: the share of the padded [rows, W] batches that is padding, 1 - total / (rows * W)
+over the timed steps (summed on the device, read once at the end).
+
+Usage: python benchmarks/varlen_tokens.py [--steps K] [--decode device|host] [--layout padded|packed]
 """
 import argparse
 import json
@@ -33,6 +38,7 @@ def main():
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--decode", default="auto", choices=["auto", "device", "host"])
     ap.add_argument("--h2d", default="auto", choices=["auto", "dma", "zerocopy"])
+    ap.add_argument("--layout", default="padded", choices=["padded", "packed"])
     ap.add_argument("--coalesce", type=int, default=None, help="batches per launch (default: the loader's)")
     ap.add_argument("--lockstep", default="off", choices=["off", "rccl"],
                     help="rccl: the per-step RCCL agreement at world 1 (a one-rank nccl group), as under DDP")
@@ -67,22 +73,52 @@ def main():
         dl = DeviceLoader(Tokens.placeholder(), B, num_workers=args.workers, device=args.device, dtype=torch.int64,
                           decode=args.decode, h2d=args.h2d, lockstep="rccl" if args.lockstep == "rccl" else True,
                           **({"coalesce": args.coalesce} if args.coalesce else {}),
+                          **({"layout": "packed"} if args.layout == "packed" else {}),
                           worker_init_fn=Tokens.init_worker("tok", bootstrap_servers=url, group_id="tok",
                                                             auto_offset_reset="earliest"))
+        packed = args.layout == "packed"
+        # padding_fraction: the real (non-padding) elements are summed on the device -- `lengths` (padded) or
+        # `total` (packed) of 64 steps at a time, three small launches per 64 steps -- and read once after the
+        # timed loop.  The warm-up folds too: the first call of a torch kernel loads its code object, which
+        # alone costs about as much as the whole timed window.
+        real = torch.zeros((), dtype=torch.int64, device=args.device)
+        held = []
+
+        def fold():
+            real.add_((torch.stack(held) if packed else torch.cat(held)).sum())
+            held.clear()
+
         it = iter(auto_commit(dl))
         for _ in range(args.warmup):
-            x, lens = next(it)
+            item = next(it)
+            held.append(item.total if packed else item[1])
+        if held:
+            fold()
         mirror_on = bool(getattr(dl._run, "mirror", False))
         transport = dict(dl.lockstep_info).get("transport")
+        real.zero_()
         torch.cuda.synchronize()
         dl.reset_stats()
         t0 = time.perf_counter()
-        rows = 0
+        rows = cells = 0
         for _ in range(args.steps):
-            x, lens = next(it)
-            rows += x.shape[0]
+            item = next(it)
+            if packed:
+                x = item.values
+                rows += item.cu_seqlens.shape[0] - 1  # cells: the default capacity is rows * W
+                held.append(item.total)
+            else:
+                x, lens = item
+                rows += x.shape[0]
+                held.append(lens)
+            cells += x.numel()
+            if len(held) == 64:
+                fold()
+        if held:
+            fold()
         torch.cuda.synchronize()
         el = time.perf_counter() - t0
+        padding = 1.0 - int(real) / max(1, cells)
         st = dl.stats_summary()
         decode = (("device (varlen_span_kernel from an HBM mirror filled by SDMA copies)" if mirror_on
                    else "device (varlen_span_kernel from the pinned logs)") if dl.plan.var_span else "host workers")
@@ -91,7 +127,8 @@ def main():
         if args.lockstep == "rccl":
             torch.distributed.destroy_process_group()
         rec_bytes = b.partition_stats("tok", 0)["log_bytes"] / max(1, b.end_offset("tok", 0))
-        print(json.dumps({"metric": "int32 token records/s to GPU (int64 padded), per-batch commit",
+        print(json.dumps({"metric": f"int32 token records/s to GPU (int64 {args.layout}), per-batch commit",
+                          "layout": args.layout, "padding_fraction": round(padding, 4),
                           "value": round(rows / el), "ms_per_step": round(el / args.steps * 1e3, 4),
                           "timed_s": round(el, 4), "steps": args.steps, "batch_size": B, "workers": args.workers,
                           "decode": decode, "h2d": args.h2d, "lockstep": transport,

@@ -8,7 +8,10 @@ effective HBM bandwidth (bytes read + bytes written) / time, next to the equival
 PyTorch op (``Tensor.to`` for the cast, an index_put-based pad for var-len); ``eager_us``
 is the wall time per eager call including the Python wrapper and launch.
 
-Usage: python tools/kernel_bench.py [--quick] [--iters N]
+``pack_rows`` (padded -> packed cu_seqlens layout, pack.hip) has no single PyTorch kernel to stand
+beside: a boolean-mask gather synchronises with the host, so it cannot be graph-timed.
+
+Usage: python tools/kernel_bench.py [--quick] [--iters N] [--only pack_rows]
 """
 import argparse
 import json
@@ -63,10 +66,59 @@ def timeit_graph(fn, iters, per_graph=20):
     return a.elapsed_time(b) * 1000.0 / (reps * per_graph)
 
 
+def pack_rows_cases(dev, iters):
+    """Padded [256, 512] with lengths U(64, 512) -- benchmarks/varlen_tokens.py's batch -- packed by
+    one launch: GPU time per launch and (kept elements read + capacity elements written, plus the
+    lengths / cu_seqlens / ids traffic) / time.  ``eager_us``: wall time per ``pack_padded`` call (checks, pad
+    bits, allocations, launch); ``loader_entry_us``: per ``pack_launch`` call, the loader's per-batch entry."""
+    import torch
+
+    from torchkafka_amd.ops.collate import pack_launch, pack_padded, pad_bits
+    from torchkafka_amd.ops.native import hip
+
+    mod = hip()
+    g = torch.Generator().manual_seed(1)
+    rows, W = 256, 512
+    lens = torch.randint(64, W + 1, (rows,), generator=g)
+    lens_d = lens.to(dev)
+    total, cap = int(lens.sum()), rows * W
+    res = []
+    for name, dt, ids in (("256 rows, L~U(64,512) int64", torch.int64, False),
+                          ("256 rows, L~U(64,512) bf16", torch.bfloat16, False),
+                          ("256 rows, L~U(64,512) int64 + position/segment ids", torch.int64, True)):
+        padded = torch.randint(0, 1 << 15, (rows, W), generator=g).to(dt).to(dev)
+        esz = padded.element_size()
+        values = torch.empty(cap, dtype=dt, device=dev)
+        cu = torch.empty(rows + 1, dtype=torch.int32, device=dev)
+        tot = torch.empty((), dtype=torch.int64, device=dev)
+        pos = torch.empty(cap, dtype=torch.int32, device=dev) if ids else None
+        seg = torch.empty(cap, dtype=torch.int32, device=dev) if ids else None
+        bits = pad_bits(dt, 0)
+
+        def ours():
+            mod.pack_rows(padded.data_ptr(), esz, rows, W, lens_d.data_ptr(), values.data_ptr(), cap, bits,
+                          cu.data_ptr(), tot.data_ptr(), pos.data_ptr() if ids else 0, seg.data_ptr() if ids else 0,
+                          torch.cuda.current_stream(dev).cuda_stream)
+
+        ours()
+        keep = torch.arange(W)[None, :] < lens[:, None]
+        assert torch.equal(values[:total].cpu(), padded.cpu()[keep]) and int(tot) == total
+        assert int(cu[-1]) == total and not bool(values[total:].any())
+        nbytes = total * esz + cap * esz + rows * 8 + (rows + 1) * 4 + (2 * cap * 4 if ids else 0)
+        g_ours = timeit_graph(ours, iters)
+        t_op = timeit(lambda: pack_padded(padded, lens_d, None, 0, ids), iters)
+        t_entry = timeit(lambda: pack_launch(padded, lens_d, cap, bits, ids), iters)  # what the loader calls per batch
+        res.append({"kernel": "pack_rows", "case": name, "gpu_us": round(g_ours, 2),
+                    "GBps": round(nbytes / g_ours / 1e3, 1), "padding_fraction": round(1 - total / cap, 3),
+                    "eager_us": round(t_op, 2), "loader_entry_us": round(t_entry, 2)})
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true", help="fewer iterations (for counter collection)")
     ap.add_argument("--iters", type=int, default=200)
+    ap.add_argument("--only", default=None, choices=["pack_rows"], help="run only this kernel's cases")
     args = ap.parse_args()
     iters = 20 if args.quick else args.iters
 
@@ -77,6 +129,10 @@ def main():
 
     hip()
     dev = torch.device("cuda", 0)
+    if args.only == "pack_rows":
+        for r in pack_rows_cases(dev, iters):
+            print(json.dumps(r))
+        return
     out = []
 
     fixed_cases = [("config2 batch 256x256 f32->bf16", 256, 256, torch.bfloat16),
@@ -200,6 +256,7 @@ def main():
                     "text_GBps": round(text_bytes / g_ours / 1e3, 1), "numbers": int(desc[:, 2].sum()),
                     "host_parser_us_one_core": round(host_us, 1)})
 
+    out += pack_rows_cases(dev, iters)
     for r in out:
         print(json.dumps(r))
 

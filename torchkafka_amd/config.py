@@ -196,8 +196,10 @@ _CHOICES = {
     "decode": ("auto", "device", "host"),
     "json_parse": ("auto", "device", "host"),
     "multiprocessing_context": ("fork", "spawn", "forkserver"),
+    "layout": ("padded", "packed"),
 }
 _CHOICE_HELP = {
+    "layout": "'padded' ([rows, width] + lengths) or 'packed' (flat values + cu_seqlens, a PackedBatch)",
     "h2d": "'auto', 'dma' (hipMemcpyAsync on side streams), 'zerocopy' or 'direct'",
     "decode": "'auto', 'device' (gfx950 RecordBatch decode) or 'host' (worker pack)",
     "json_parse": "'auto', 'device' (gfx950 parse kernel) or 'host' (worker parse)",
@@ -224,6 +226,9 @@ class LoaderConfig:
     pad_multiple: int = 8
     pad_value: float = 0
     return_mask: bool = False
+    layout: str = "padded"
+    pack_to: Optional[int] = None
+    return_ids: bool = False
     return_info: bool = False
     native: bool = True
     multiprocessing_context: str = "fork"
@@ -260,6 +265,11 @@ class LoaderConfig:
                "lockstep must be True, False, 'host', 'rccl', 'shm' or 'always'")
         _check(self.pad_to is None or int(self.pad_to) >= 1, "pad_to must be >= 1 (or None)")
         _check(int(self.pad_multiple) >= 1, "pad_multiple must be >= 1")
+        packed = self.layout == "packed"
+        _check(not (packed and self.return_mask), "layout='packed' has no mask: return_mask=True needs layout='padded'")
+        _check(packed or self.pack_to is None, "pack_to needs layout='packed'")
+        _check(packed or not self.return_ids, "return_ids needs layout='packed'")
+        _check(self.pack_to is None or 1 <= int(self.pack_to) < 1 << 31, "pack_to must be in [1, 2^31) (or None)")
         _check(float(self.timeout) >= 0, "timeout must be >= 0 (0 waits forever)")
         _check(self.rank is None or int(self.rank) >= 0, "rank must be >= 0")
         _check(self.world_size is None or int(self.world_size) >= 1, "world_size must be >= 1")

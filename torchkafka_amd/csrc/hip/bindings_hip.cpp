@@ -110,6 +110,20 @@ PYBIND11_MODULE(_tkhip, m) {
       py::arg("rows"), py::arg("L"), py::arg("pad") = 0.0, py::arg("lengths") = 0, py::arg("mask") = 0,
       py::arg("stream") = 0);
 
+  m.attr("PACK_FUSED_ROWS") = kPackFusedRows;
+  m.def(
+      "pack_rows",
+      [](uintptr_t padded, int elem_size, int64_t rows, int64_t W, uintptr_t lengths, uintptr_t values,
+         int64_t capacity, uint64_t pad_bits, uintptr_t cu, uintptr_t total, uintptr_t pos, uintptr_t seg,
+         uintptr_t stream) {
+        launch_pack_rows(ptr<const void>(padded), elem_size, rows, W, ptr<const int64_t>(lengths), ptr<void>(values),
+                         capacity, pad_bits, ptr<int32_t>(cu), ptr<int64_t>(total), ptr<int32_t>(pos),
+                         ptr<int32_t>(seg), stream_of(stream));
+      },
+      py::arg("padded"), py::arg("elem_size"), py::arg("rows"), py::arg("W"), py::arg("lengths"), py::arg("values"),
+      py::arg("capacity"), py::arg("pad_bits") = 0, py::arg("cu_seqlens") = 0, py::arg("total") = 0,
+      py::arg("position_ids") = 0, py::arg("segment_ids") = 0, py::arg("stream") = 0);
+
   m.def(
       "launch_json_rows",
       [](uintptr_t rows, uintptr_t vals, uintptr_t out, int dst_dt, int64_t n_rows, int64_t L, double pad,

@@ -79,6 +79,15 @@ void launch_json_group(JsonGroupArgs& a, int dst_dt, hipStream_t stream);
 // Device counting of a staged group (json_span.hip): before launch_json_group on the same stream.
 void launch_json_count(const JsonGroupArgs& a, hipStream_t stream);
 
+// Padded [rows, W] (any dtype of `elem_size` 1/2/4/8 bytes) + int64 lengths[rows] -> the packed layout
+// (pack.hip): values[capacity] with the rows back to back and `pad_bits` behind them, int32
+// cu[rows + 1] clamped to capacity, the unclamped int64 *total, and -- both or neither -- int32
+// pos[capacity] / seg[capacity].  One launch up to kPackFusedRows rows, a scan launch before it above.
+constexpr int64_t kPackFusedRows = 1024;
+void launch_pack_rows(const void* padded, int elem_size, int64_t rows, int64_t W, const int64_t* lengths, void* values,
+                      int64_t capacity, uint64_t pad_bits, int32_t* cu, int64_t* total, int32_t* pos, int32_t* seg,
+                      hipStream_t stream);
+
 std::vector<std::pair<std::string, double>> api_bench(int device, int iters);
 
 }  // namespace tkh

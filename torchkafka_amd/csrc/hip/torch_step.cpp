@@ -630,6 +630,46 @@ void register_torch_step(py::module_& m) {
       "finish+commit the previous batch, take the next slot and collate it into a new tensor "
       "allocated on the current stream -> (rows, commit_status, tensor | None)");
 
+  // Padded [rows, W] + int64 lengths -> the packed layout (pack.hip), outputs allocated here on the
+  // current stream: the loader packs every batch, and five torch.empty calls through Python's
+  // argument parser cost more host time than the launch itself.
+  m.def(
+      "pack_tensors",
+      [](py::handle padded_h, py::handle lengths_h, int64_t capacity, uint64_t pad_bits, bool ids) -> py::tuple {
+        if (!THPVariable_Check(padded_h.ptr()) || !THPVariable_Check(lengths_h.ptr()))
+          throw std::invalid_argument("pack_tensors: padded and lengths must be tensors");
+        const at::Tensor& padded = THPVariable_Unpack(padded_h.ptr());
+        const at::Tensor& lengths = THPVariable_Unpack(lengths_h.ptr());
+        if (!padded.is_cuda() || padded.dim() != 2 || !padded.is_contiguous())
+          throw std::invalid_argument("pack_tensors: padded must be a contiguous [rows, W] device tensor");
+        const int64_t rows = padded.size(0), W = padded.size(1);
+        if (lengths.scalar_type() != at::kLong || lengths.dim() != 1 || lengths.size(0) != rows ||
+            !lengths.is_contiguous() || lengths.device() != padded.device())
+          throw std::invalid_argument("pack_tensors: lengths must be contiguous int64 [rows] on padded's device");
+        if (capacity < 0) throw std::invalid_argument("pack_tensors: negative capacity");
+        const auto dev = padded.device().index();
+        hipStream_t stream = c10::hip::getCurrentHIPStream(dev).stream();
+        const auto opts = padded.options();
+        at::Tensor values = at::empty({capacity}, opts);
+        at::Tensor cu = at::empty({rows + 1}, opts.dtype(at::kInt));
+        at::Tensor total = at::empty({}, opts.dtype(at::kLong));
+        at::Tensor pos, seg;
+        if (ids) {
+          pos = at::empty({capacity}, opts.dtype(at::kInt));
+          seg = at::empty({capacity}, opts.dtype(at::kInt));
+        }
+        launch_pack_rows(padded.data_ptr(), int(padded.element_size()), rows, W, lengths.data_ptr<int64_t>(),
+                         values.data_ptr(), capacity, pad_bits, cu.data_ptr<int32_t>(), total.data_ptr<int64_t>(),
+                         ids ? pos.data_ptr<int32_t>() : nullptr, ids ? seg.data_ptr<int32_t>() : nullptr, stream);
+        auto wrap = [](at::Tensor t) { return py::reinterpret_steal<py::object>(THPVariable_Wrap(std::move(t))); };
+        if (!ids) return py::make_tuple(wrap(std::move(values)), wrap(std::move(cu)), wrap(std::move(total)));
+        return py::make_tuple(wrap(std::move(values)), wrap(std::move(cu)), wrap(std::move(total)),
+                              wrap(std::move(pos)), wrap(std::move(seg)));
+      },
+      py::arg("padded"), py::arg("lengths"), py::arg("capacity"), py::arg("pad_bits") = 0, py::arg("ids") = false,
+      "-> (values [capacity], cu_seqlens int32 [rows + 1], total int64 []"
+      "[, position_ids, segment_ids int32 [capacity]]), launched on the current stream");
+
   // Coalesced variant: when several fixed-width batches are already staged, one allocation and
   // one kernel launch serve up to driver.coalesce of them; the following calls return the
   // pre-collated tensors without any HIP call (MainDriver::step_group_begin/launch).

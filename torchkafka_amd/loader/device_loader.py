@@ -37,7 +37,8 @@ import torch
 
 from ..client.errors import CorruptRecordException
 from ..config import LoaderConfig
-from ..ops.collate import CODE_DTYPE, DTYPE_CODE, FLOAT_DTYPES, _stream_ptr, normalize_params
+from ..ops.collate import (CODE_DTYPE, DTYPE_CODE, FLOAT_DTYPES, PackedBatch, _stream_ptr, normalize_params,
+                           pack_launch, pad_bits, reference_packed)
 from ..ops.native import core, hip
 from ..parallel.sharding import dist_rank_world
 from ..utils.metrics import LoaderStats
@@ -64,7 +65,7 @@ def _traced_step(step):
 class KafkaBatch(NamedTuple):
     """Batch plus provenance (``return_info=True``)."""
 
-    data: torch.Tensor
+    data: torch.Tensor    # layout="packed": a PackedBatch (lengths and mask are then None)
     lengths: torch.Tensor | None
     mask: torch.Tensor | None
     watermarks: list      # [(pidx, first_offset, next_offset, n_records)]
@@ -108,6 +109,18 @@ class DeviceLoader(LoaderBridges, LoaderCommits, LoaderLockstep):
         pad_multiple: with ``pad_to=None``, the batch width is rounded up to a multiple of this.
         pad_value: the value written into the padding.
         return_mask: var-len / JSON batches also yield a bool ``[rows, width]`` mask of real elements.
+        layout: ``"padded"`` (default: var-len / JSON batches are ``[rows, width]`` + lengths) or ``"packed"``:
+            each batch is a :class:`~torchkafka_amd.PackedBatch` -- flat ``values[capacity]`` with the rows back
+            to back and the pad value behind them, int32 ``cu_seqlens[rows + 1]``, ``max_seqlen`` (the padded
+            width, an upper bound on the longest row; exact with ``pad_to=None, pad_multiple=1``) and a 0-dim
+            device ``total`` -- made from the padded batch by one more gfx950 launch (csrc/hip/pack.hip).
+            ``pad_to``, ``pad_multiple``, ``pad_value``, ``dtype`` and the schema's ``max_len`` / ``truncate``
+            keep their meaning; there is no mask.  Fixed-width and structured schemas raise ``TypeError``.
+        pack_to: ``layout="packed"``: the capacity of every batch's ``values`` (static shapes with
+            ``drop_last=True``, e.g. for graph capture).  Rows beyond it are cut: ``cu_seqlens`` is clamped to it
+            and ``total > pack_to`` shows the overflow, without a sync.  None: ``rows * width``, nothing is ever cut.
+        return_ids: ``layout="packed"``: also int32 ``position_ids`` / ``segment_ids`` ``[capacity]`` (index inside
+            the row / row index; 0 / -1 behind the last row).
         drop_last: drop a final batch shorter than ``batch_size`` (DataLoader's meaning).
         return_info: yield ``(batch, BatchInfo)`` with each batch's partitions and offset ranges.
         native: use the native step driver (``False``: the Python loop, for debugging).
@@ -221,6 +234,13 @@ class DeviceLoader(LoaderBridges, LoaderCommits, LoaderLockstep):
         self.pad_multiple = int(cfg.pad_multiple)
         self.pad_value = cfg.pad_value
         self.return_mask = cfg.return_mask
+        self.layout = cfg.layout
+        self.pack_to = None if cfg.pack_to is None else int(cfg.pack_to)
+        self.return_ids = bool(cfg.return_ids)
+        if self.layout == "packed" and getattr(self.schema, "kind", None) not in (1, 2):
+            raise TypeError("layout='packed' needs a VarLen or JsonArray schema (fixed-width and structured "
+                            "samples have no row lengths to pack)")
+        self._pad_bits: dict = {}
         self.return_info = cfg.return_info
         self.native = cfg.native
         self.multiprocessing_context = cfg.multiprocessing_context
@@ -641,7 +661,18 @@ class DeviceLoader(LoaderBridges, LoaderCommits, LoaderLockstep):
         drv.configure_varlen(self.device.index, DTYPE_CODE[dst_dt], -1 if self.pad_to is None else int(self.pad_to),
                              self.pad_multiple, float(self.pad_value), bool(self.return_mask), native_ac, 100,
                              self.verify == "deliver")
-        return drv.varlen_fast_next
+        if self.layout != "packed":
+            return drv.varlen_fast_next
+        native, pack = drv.varlen_fast_next, self._pack
+
+        def step():
+            # the native step ordered the current stream behind the decode (wait_group) before it
+            # handed the padded batch out, so the pack kernel goes on that stream right behind it
+            r, cs, item = native()
+            if item is not None:
+                item = pack(item[0], item[1])
+            return r, cs, item
+        return step
 
     def _slot_stage(self, run: _Run, auto_commit: bool, debug: bool):
         drv = run.driver
@@ -762,10 +793,14 @@ class DeviceLoader(LoaderBridges, LoaderCommits, LoaderLockstep):
                 out = out.view(-1)[:n_rows * W].view(n_rows, W)
                 if mask is not None:
                     mask = mask.view(-1)[:n_rows * W].view(n_rows, W)
+        if not fixed and self.layout == "packed":
+            out, lengths = self._pack(out, lengths), None
         self.stats.record_batch(n_rows, payload_bytes, t1 - t0, time.perf_counter_ns() - t1)
         n_rec = sum(w[3] for w in wms)
         if self.return_info:
             return KafkaBatch(out, lengths, mask, wms, n_rec), wms
+        if lengths is None and not fixed:
+            return out, wms
         if fixed:
             return out, wms
         return ((out, lengths, mask) if self.return_mask else (out, lengths)), wms
@@ -860,12 +895,37 @@ class DeviceLoader(LoaderBridges, LoaderCommits, LoaderLockstep):
                 if mask is not None:
                     mask.copy_(res[2])
                 run.ring.main_release(g)
+        if not fixed and self.layout == "packed":
+            out, lengths = self._pack(out, lengths), None
         n_rec = sum(w[3] for w in wms)
         if self.return_info:
             return KafkaBatch(out, lengths, mask, wms, n_rec)
         if fixed:
             return out if ext is None else self._with_fields(out, ext)
+        if lengths is None:
+            return out
         return (out, lengths, mask) if self.return_mask else (out, lengths)
+
+    def _pack(self, out: torch.Tensor, lengths: torch.Tensor) -> PackedBatch:
+        """A delivered padded batch -> its PackedBatch, by one launch on the current stream (the
+        stream the batch is delivered on; every route has ordered it behind the decode by now).
+
+        The padded tensor and its lengths are dropped when this returns.  That is safe for the same
+        reason a user may drop a delivered batch right after launching work on it: a block the
+        native step allocated on a decode stream was recorded on the delivery stream
+        (torch_step.cpp alloc_group / alloc_json_group: recordStream), so the caching allocator
+        hands it out again only after an event behind this launch; every other route allocates on
+        the delivery stream itself, where reuse is ordered behind the launch by the stream."""
+        rows, W = out.shape
+        cap = rows * W if self.pack_to is None else self.pack_to
+        if out.device.type != "cuda":
+            return reference_packed(out, lengths, cap, self.pad_value, self.return_ids)
+        if rows * W >= 1 << 31:
+            raise ValueError("layout='packed': rows * width must be below 2^31")
+        bits = self._pad_bits.get(out.dtype)
+        if bits is None:
+            bits = self._pad_bits[out.dtype] = pad_bits(out.dtype, self.pad_value)
+        return pack_launch(out, lengths, cap, bits, self.return_ids)
 
     def _with_fields(self, out, ext):
         """(values, fields...) in the order the schema added them (native columns: key first)."""

@@ -6,6 +6,8 @@ kernels through the H2D engine on its pinned staging buffers.
 """
 from __future__ import annotations
 
+from typing import NamedTuple
+
 import torch
 
 from .native import hip
@@ -86,6 +88,93 @@ def collate_varlen(offsets: torch.Tensor, values: torch.Tensor, dtype: torch.dty
     return (out, lengths, mask) if return_mask else (out, lengths)
 
 
+# ----------------------------------------------------------------------------- packed (cu_seqlens) layout
+class PackedBatch(NamedTuple):
+    """A var-len batch without padding between its rows (``layout="packed"``).
+
+    ``values[cu_seqlens[r]:cu_seqlens[r + 1]]`` is row ``r``; elements from ``cu_seqlens[-1]`` up to
+    the capacity ``values.numel()`` hold the pad value.
+
+    Fields:
+        values: 1-D ``[capacity]`` in the output dtype.
+        cu_seqlens: int32 ``[rows + 1]``, ``cu_seqlens[0] == 0``, clamped to the capacity: a row that
+            does not fit is cut there and the rows after it are empty.
+        max_seqlen: the width ``W`` of the padded batch this was packed from -- an upper BOUND on the
+            longest row (exact only with ``pad_to=None, pad_multiple=1``).
+        total: 0-dim int64 device tensor, the unclamped sum of the lengths; ``total > capacity``
+            means rows were cut.  Reading it synchronises, so the loader never does.
+        position_ids: int32 ``[capacity]`` (``return_ids=True``): ``i`` for element ``i`` of its row, 0 in the tail.
+        segment_ids: int32 ``[capacity]`` (``return_ids=True``): the row index, -1 in the tail.
+    """
+
+    values: torch.Tensor
+    cu_seqlens: torch.Tensor
+    max_seqlen: int
+    total: torch.Tensor
+    position_ids: torch.Tensor | None = None
+    segment_ids: torch.Tensor | None = None
+
+    def trim(self) -> torch.Tensor:
+        """``values[:min(total, capacity)]``: the real elements only.  SYNCHRONISES with the device
+        (it reads ``total``); keep the fixed-capacity ``values`` where shapes must stay static."""
+        return self.values[:min(int(self.total.item()), self.values.numel())]
+
+
+_BITS_VIEW = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}
+_PACK_LIMIT = 1 << 31  # cu_seqlens is int32
+
+
+def pad_fill(dtype: torch.dtype, pad_value: float = 0) -> torch.Tensor:
+    """``pad_value`` as one CPU element of ``dtype``, rounded as the padded path rounds it (floats
+    through f32, integers through int64)."""
+    if dtype in FLOAT_DTYPES:
+        return torch.tensor(float(pad_value), dtype=torch.float32).to(dtype)
+    return torch.tensor(int(pad_value), dtype=torch.int64).to(dtype)
+
+
+def pad_bits(dtype: torch.dtype, pad_value: float = 0) -> int:
+    """The bit pattern of :func:`pad_fill` as an unsigned int (what the pack kernel stores)."""
+    fill = pad_fill(dtype, pad_value)
+    esz = fill.element_size()
+    return int(fill.view(_BITS_VIEW[esz]).item()) & ((1 << (8 * esz)) - 1)
+
+
+def _pack_capacity(padded: torch.Tensor, lengths: torch.Tensor, capacity) -> tuple[int, int, int]:
+    if padded.dim() != 2:
+        raise ValueError("pack: padded must be [rows, width]")
+    rows, W = padded.shape
+    if lengths.dim() != 1 or lengths.numel() != rows:
+        raise ValueError("pack: lengths must be [rows]")
+    if padded.element_size() not in _BITS_VIEW:
+        raise TypeError(f"pack: unsupported dtype {padded.dtype}")
+    cap = rows * W if capacity is None else int(capacity)
+    if cap < 0 or cap >= _PACK_LIMIT or rows * W >= _PACK_LIMIT:
+        raise ValueError("pack: capacity and rows * width must be in [0, 2^31)")
+    return rows, W, cap
+
+
+def pack_launch(padded: torch.Tensor, lengths: torch.Tensor, cap: int, bits: int, return_ids: bool) -> PackedBatch:
+    """The pack kernel on the current stream; ``padded`` contiguous ``[rows, W]`` on the GPU,
+    ``lengths`` contiguous int64, ``bits`` from :func:`pad_bits` (the loader's per-batch entry: no checks)."""
+    out = hip().pack_tensors(padded, lengths, cap, bits, return_ids)  # allocates the outputs natively
+    if return_ids:
+        return PackedBatch(out[0], out[1], padded.shape[1], out[2], out[3], out[4])
+    return PackedBatch(out[0], out[1], padded.shape[1], out[2])
+
+
+def pack_padded(padded: torch.Tensor, lengths: torch.Tensor, capacity: int | None = None, pad_value: float = 0,
+                return_ids: bool = False) -> PackedBatch:
+    """Padded ``[rows, W]`` + ``lengths`` [rows] -> :class:`PackedBatch` of ``capacity`` elements
+    (default ``rows * W``: nothing is ever cut), in one gfx950 launch on the current stream (two above
+    ``hip().PACK_FUSED_ROWS`` rows).  A length below 0 counts as 0, one above ``W`` as ``W``.  CPU
+    tensors take :func:`reference_packed`."""
+    if padded.device.type != "cuda":
+        return reference_packed(padded, lengths, capacity, pad_value, return_ids)
+    rows, W, cap = _pack_capacity(padded, lengths, capacity)
+    lengths = lengths.to(device=padded.device, dtype=torch.int64).contiguous()
+    return pack_launch(padded.contiguous(), lengths, cap, pad_bits(padded.dtype, pad_value), return_ids)
+
+
 # ----------------------------------------------------------------------------- torch references
 def reference_fixed(src: torch.Tensor, dtype: torch.dtype, normalize=None) -> torch.Tensor:
     if normalize is None:
@@ -120,3 +209,31 @@ def reference_varlen(offsets: torch.Tensor, values: torch.Tensor, dtype: torch.d
         mask = torch.arange(L, device=values.device)[None, :] < lengths[:, None]
         return out, lengths, mask
     return out, lengths
+
+
+def reference_packed(padded: torch.Tensor, lengths: torch.Tensor, capacity: int | None = None, pad_value: float = 0,
+                     return_ids: bool = False) -> PackedBatch:
+    """:func:`pack_padded` in plain torch (the CPU path).  Works on integer views of the element
+    size, so fp8 values and NaN payloads pass through untouched."""
+    rows, W, cap = _pack_capacity(padded, lengths, capacity)
+    dev = padded.device
+    ib = _BITS_VIEW[padded.element_size()]
+    src = padded.contiguous().view(ib)
+    lens = lengths.to(device=dev, dtype=torch.int64).clamp(0, W)
+    ends = torch.cumsum(lens, 0)  # int64
+    total = ends[-1].clone() if rows else torch.zeros((), dtype=torch.int64, device=dev)
+    cu = torch.zeros(rows + 1, dtype=torch.int64, device=dev)
+    cu[1:] = ends.clamp(max=cap)
+    kept_per_row = cu[1:] - cu[:-1]
+    kept = int(cu[-1])
+    values = torch.full((cap,), int(pad_fill(padded.dtype, pad_value).view(ib).item()), dtype=ib, device=dev)
+    row_idx = torch.repeat_interleave(torch.arange(rows, device=dev), kept_per_row)
+    col_idx = torch.arange(kept, device=dev) - torch.repeat_interleave(cu[:-1], kept_per_row)
+    values[:kept] = src[row_idx, col_idx]
+    pos = seg = None
+    if return_ids:
+        pos = torch.zeros(cap, dtype=torch.int32, device=dev)
+        seg = torch.full((cap,), -1, dtype=torch.int32, device=dev)
+        pos[:kept] = col_idx.to(torch.int32)
+        seg[:kept] = row_idx.to(torch.int32)
+    return PackedBatch(values.view(padded.dtype), cu.to(torch.int32), W, total, pos, seg)
