@@ -52,12 +52,15 @@ const char* parse_number(const char* p, const char* e, double* out) {
   uint64_t mant = 0;
   int nd = 0, exp10 = 0;
   bool any = false, truncated = false;
+  const char* ip = p;
   while (p < e && is_digit(*p)) {
     const int d = *p++ - '0';
     any = true;
     if (mant == 0 && d == 0) continue;
     if (nd < 19) { mant = mant * 10 + uint64_t(d); ++nd; } else { ++exp10; truncated = true; }
   }
+  // json.loads' integer part: "0" or [1-9][0-9]*, never empty ("01", "-00", ".5" are errors)
+  if (p == ip || (*ip == '0' && p - ip > 1)) return nullptr;
   const bool is_int_so_far = !(p < e && (*p == '.' || *p == 'e' || *p == 'E'));
   if (p < e && *p == '.') {
     ++p;

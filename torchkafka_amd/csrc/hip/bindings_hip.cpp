@@ -134,6 +134,56 @@ PYBIND11_MODULE(_tkhip, m) {
       py::arg("rows"), py::arg("values"), py::arg("out"), py::arg("dst_dtype"), py::arg("n_rows"), py::arg("L"),
       py::arg("pad") = 0.0, py::arg("lengths") = 0, py::arg("mask") = 0, py::arg("err") = 0, py::arg("stream") = 0);
 
+  // The driver's group launch for the kernel tests: 1..kMaxGroup batches, each with its own
+  // descriptors, staged values, output and count words (plain device memory: the kernels only
+  // store to info and err).  count_first: json_count_kernel, then the parse, on the one stream.
+  m.attr("JSON_MAX_GROUP") = kMaxGroup;
+  m.attr("JSON_COUNT_ON_DEVICE") = int(tk::kJsonCountOnDevice);
+  m.def(
+      "launch_json_group",
+      [](const std::vector<uintptr_t>& desc, const std::vector<uintptr_t>& vals, const std::vector<uint64_t>& vals_cap,
+         const std::vector<uintptr_t>& out, const std::vector<int64_t>& L, const std::vector<int64_t>& n_rows,
+         const std::vector<uintptr_t>& lengths, const std::vector<uintptr_t>& mask, const std::vector<uintptr_t>& err,
+         const std::vector<uintptr_t>& ctr, const std::vector<uint32_t>& ctr_tag, const std::vector<int32_t>& trunc,
+         const std::vector<uintptr_t>& info, int dst_dt, double pad, int32_t mult, int32_t err_tag, bool fused_count,
+         bool count_first, uintptr_t stream) {
+        const size_t n = desc.size();
+        if (n < 1 || n > size_t(kMaxGroup)) throw std::invalid_argument("launch_json_group: 1..kMaxGroup batches");
+        for (size_t sz : {vals.size(), vals_cap.size(), out.size(), L.size(), n_rows.size(), lengths.size(),
+                          mask.size(), err.size(), ctr.size(), ctr_tag.size(), trunc.size(), info.size()})
+          if (sz != n) throw std::invalid_argument("launch_json_group: one entry per batch in every sequence");
+        if (fused_count && (mult != 0 || count_first))
+          throw std::invalid_argument("launch_json_group: fused_count goes with mult 0 and no count launch");
+        JsonGroupArgs a{};
+        a.n = int(n);
+        a.pad = float(pad);
+        a.mult = mult;
+        a.err_tag = err_tag;
+        a.fused_count = fused_count ? 1 : 0;
+        for (size_t k = 0; k < n; ++k) {
+          if (n_rows[k] < 0 || L[k] < 0) throw std::invalid_argument("launch_json_group: negative rows or L");
+          a.row_base[k + 1] = a.row_base[k] + n_rows[k];
+          a.rows[k] = ptr<const JsonRowDesc>(desc[k]);
+          a.vals[k] = ptr<const uint8_t>(vals[k]);
+          a.vals_cap[k] = vals_cap[k];
+          a.out[k] = ptr<void>(out[k]);
+          a.L[k] = L[k];
+          a.lengths[k] = ptr<int64_t>(lengths[k]);
+          a.mask[k] = ptr<uint8_t>(mask[k]);
+          a.err[k] = ptr<int32_t>(err[k]);
+          a.ctr[k] = ptr<const unsigned long long>(ctr[k]);
+          a.ctr_tag[k] = ctr_tag[k];
+          a.trunc[k] = trunc[k];
+          a.info[k] = ptr<int32_t>(info[k]);
+        }
+        if (count_first) launch_json_count(a, stream_of(stream));
+        launch_json_group(a, dst_dt, stream_of(stream));
+      },
+      py::arg("desc"), py::arg("values"), py::arg("vals_cap"), py::arg("out"), py::arg("L"), py::arg("n_rows"),
+      py::arg("lengths"), py::arg("mask"), py::arg("err"), py::arg("ctr"), py::arg("ctr_tag"), py::arg("trunc"),
+      py::arg("info"), py::arg("dst_dtype"), py::arg("pad") = 0.0, py::arg("mult") = 1, py::arg("err_tag") = 0,
+      py::arg("fused_count") = false, py::arg("count_first") = false, py::arg("stream") = 0);
+
   py::class_<Engine>(m, "Engine")
       .def(py::init<int, int, size_t, int, int>(), py::arg("device"), py::arg("n_slots"), py::arg("staging_bytes"),
            py::arg("n_streams") = 4, py::arg("mode") = int(kH2DDma))
