@@ -4,6 +4,10 @@ The kernel reads record values straight out of the pinned broker logs, verifies 
 every RecordBatch (kafka-python's check_crcs, reference kafka_dataset.py:156 loop) and casts the
 values; every case is compared bit for bit with the host path (decode='host': workers CRC-check
 and pack, the collate kernel casts), which tests/test_gpu_kernels.py pins to Tensor.to.
+
+Everything here goes through a broker and a worker, so it sees the segments the worker happens to
+cut.  The kernel-level pins -- raw partial CRCs against an independent CRC32C, window geometry,
+segment parts, stray stores -- are in tests/test_gpu_span_kernels.py.
 """
 import os
 import random

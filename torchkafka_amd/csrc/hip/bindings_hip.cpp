@@ -49,6 +49,37 @@ class PyLockstep : public LockstepTransport {
 template <typename T>
 T* ptr(uintptr_t p) { return reinterpret_cast<T*>(p); }
 hipStream_t stream_of(uintptr_t s) { return reinterpret_cast<hipStream_t>(s); }
+
+// The per-segment sequences of launch_span_group / launch_var_span_group -> SpanDevSeg[]; returns
+// the segment count.  `nb`: batches of the launch (every segment names one of them).
+int fill_span_segs(SpanDevSeg* s, const char* what, size_t nb, const std::vector<uintptr_t>& src,
+                   const std::vector<uint64_t>& log_pos, const std::vector<uint32_t>& len,
+                   const std::vector<uint32_t>& flags, const std::vector<uint32_t>& crc,
+                   const std::vector<uint32_t>& row_begin, const std::vector<uint32_t>& row_end,
+                   const std::vector<uint32_t>& batch, const std::vector<uint32_t>& seg) {
+  const std::string w(what);
+  const size_t n = src.size();
+  if (n < 1 || n > size_t(kMaxLaunchSegs)) throw std::invalid_argument(w + ": 1..kMaxLaunchSegs segments");
+  for (size_t sz : {log_pos.size(), len.size(), flags.size(), crc.size(), row_begin.size(), row_end.size(),
+                    batch.size(), seg.size()})
+    if (sz != n) throw std::invalid_argument(w + ": one entry per segment in every sequence");
+  for (size_t i = 0; i < n; ++i) {
+    if (batch[i] >= nb) throw std::invalid_argument(w + ": a segment names a batch the launch does not have");
+    if (seg[i] > 0xFFFFu) throw std::invalid_argument(w + ": segment index past 16 bits");
+    SpanDevSeg& d = s[i];
+    d = SpanDevSeg{};
+    d.src = ptr<const uint8_t>(src[i]);
+    d.log_pos = log_pos[i];
+    d.len = len[i];
+    d.flags = flags[i];
+    d.crc = crc[i];
+    d.row_begin = row_begin[i];
+    d.row_end = row_end[i];
+    d.batch = uint16_t(batch[i]);
+    d.seg = uint16_t(seg[i]);
+  }
+  return int(n);
+}
 }  // namespace
 
 #ifndef TK_SOURCES_SHA
@@ -183,6 +214,130 @@ PYBIND11_MODULE(_tkhip, m) {
       py::arg("lengths"), py::arg("mask"), py::arg("err"), py::arg("ctr"), py::arg("ctr_tag"), py::arg("trunc"),
       py::arg("info"), py::arg("dst_dtype"), py::arg("pad") = 0.0, py::arg("mult") = 1, py::arg("err_tag") = 0,
       py::arg("fused_count") = false, py::arg("count_first") = false, py::arg("stream") = 0);
+
+  // The span kernels for the kernel tests (tests/test_gpu_span_kernels.py): a SpanLaunch /
+  // VarSpanLaunch filled from Python, every pointer plain device memory (the kernels only load
+  // from src, row_pos, rows, slot and tabs, and only store to the others).  What the driver
+  // derives -- vector stores, the aligned var-len path -- is checked against the driver's condition
+  // (driver_launch.cpp) here, so a test cannot reach a misaligned vector store; everything else
+  // is check_span_decode / check_var_span, which the launch functions run for the driver too.
+  // dry_run: only the checks -- what a test of the refusals passes, so that a check that went
+  // missing shows as a red test and not as a launch on the test's made-up addresses.
+  m.attr("SPAN_WIN") = tk::kSpanWin;
+  m.attr("SPAN_PIECE") = tk::kSpanPiece;
+  m.attr("SPAN_TAB_WORDS") = tk::kSpanTabWords;
+  m.attr("SPAN_MAX_PARTS") = int(tk::kSpanMaxParts);
+  m.attr("MAX_LAUNCH_SEGS") = kMaxLaunchSegs;
+  m.attr("MAX_GROUP") = kMaxGroup;
+  m.attr("SEG_CRC_FIRST") = int(tk::kSegCrcFirst);
+  m.attr("SEG_CRC_LAST") = int(tk::kSegCrcLast);
+  m.attr("SEG_CRC") = int(tk::kSegCrc);
+  m.attr("SEG_HOST_ROWS") = int(tk::kSegHostRows);
+  m.def(
+      "launch_span_group",
+      [](const std::vector<uintptr_t>& src, const std::vector<uint64_t>& log_pos, const std::vector<uint32_t>& len,
+         const std::vector<uint32_t>& flags, const std::vector<uint32_t>& crc, const std::vector<uint32_t>& row_begin,
+         const std::vector<uint32_t>& row_end, const std::vector<uint32_t>& batch, const std::vector<uint32_t>& seg,
+         const std::vector<uintptr_t>& out, const std::vector<uintptr_t>& row_pos, const std::vector<uintptr_t>& err,
+         const std::vector<uintptr_t>& partials, const std::vector<uintptr_t>& ext_out,
+         const std::vector<uintptr_t>& ext_src, const std::vector<uint32_t>& ext_words, int64_t row_elems,
+         bool vec_store, uintptr_t tabs, int parts, uintptr_t part_acc, int src_dt, int dst_dt, uintptr_t shift,
+         uintptr_t scale, uintptr_t stream, bool dry_run) {
+        const char* what = "launch_span_group";
+        const std::string w(what);
+        const size_t nb = out.size();
+        if (nb < 1 || nb > size_t(kMaxGroup)) throw std::invalid_argument(w + ": 1..kMaxGroup batches");
+        for (size_t sz : {row_pos.size(), err.size(), partials.size(), ext_out.size(), ext_src.size(), ext_words.size()})
+          if (sz != nb) throw std::invalid_argument(w + ": one entry per batch in every sequence");
+        if (parts > 1 && part_acc % 8 != 0) throw std::invalid_argument(w + ": part_acc must be 8-byte aligned");
+        SpanLaunch a{};
+        a.n_seg = fill_span_segs(a.s, what, nb, src, log_pos, len, flags, crc, row_begin, row_end, batch, seg);
+        // vector stores: MainDriver::launch_span's condition
+        const int ssz = dtype_size(src_dt), dsz = dtype_size(dst_dt);
+        const int per = ssz > 0 ? 16 / ssz : 1;
+        bool vec = ssz > 0 && row_elems % per == 0 && (row_elems * dsz) % 16 == 0;
+        for (size_t k = 0; k < nb; ++k) {
+          vec = vec && out[k] % 16 == 0;
+          if (ext_words[k] && (ext_out[k] == 0 || ext_src[k] == 0 || ext_out[k] % 8 != 0 || ext_src[k] % 8 != 0))
+            throw std::invalid_argument(w + ": ext_words without aligned ext_out / ext_src");
+          a.b[k].out = ptr<void>(out[k]);
+          a.b[k].row_pos = ptr<const uint64_t>(row_pos[k]);
+          a.b[k].err = ptr<int32_t>(err[k]);
+          a.b[k].partials = ptr<uint32_t>(partials[k]);
+          a.b[k].ext_out = ptr<int64_t>(ext_out[k]);
+          a.b[k].ext_src = ptr<const int64_t>(ext_src[k]);
+          a.b[k].ext_words = ext_words[k];
+        }
+        if (vec_store && !vec)
+          throw std::invalid_argument(w + ": vec_store needs whole 16-byte groups and 16-byte aligned rows");
+        a.vec_store = vec_store ? 1 : 0;
+        a.row_elems = row_elems;
+        a.tabs = ptr<const uint32_t>(tabs);
+        a.parts = parts;
+        a.part_acc = ptr<uint32_t>(part_acc);
+        check_span_decode(a, src_dt, dst_dt, ptr<const float>(shift), ptr<const float>(scale));
+        if (!dry_run)
+          launch_span_decode(a, src_dt, dst_dt, ptr<const float>(shift), ptr<const float>(scale), stream_of(stream));
+      },
+      py::arg("src"), py::arg("log_pos"), py::arg("len"), py::arg("flags"), py::arg("crc"), py::arg("row_begin"),
+      py::arg("row_end"), py::arg("batch"), py::arg("seg"), py::arg("out"), py::arg("row_pos"), py::arg("err"),
+      py::arg("partials"), py::arg("ext_out"), py::arg("ext_src"), py::arg("ext_words"), py::arg("row_elems"),
+      py::arg("vec_store"), py::arg("tabs"), py::arg("parts") = 1, py::arg("part_acc") = 0,
+      py::arg("src_dtype") = int(kF32), py::arg("dst_dtype") = int(kF32), py::arg("shift") = 0, py::arg("scale") = 0,
+      py::arg("stream") = 0, py::arg("dry_run") = false);
+  m.def(
+      "launch_var_span_group",
+      [](const std::vector<uintptr_t>& src, const std::vector<uint64_t>& log_pos, const std::vector<uint32_t>& len,
+         const std::vector<uint32_t>& flags, const std::vector<uint32_t>& crc, const std::vector<uint32_t>& row_begin,
+         const std::vector<uint32_t>& row_end, const std::vector<uint32_t>& batch, const std::vector<uint32_t>& seg,
+         const std::vector<uintptr_t>& out, const std::vector<uintptr_t>& rows, const std::vector<uintptr_t>& slot,
+         const std::vector<uintptr_t>& lengths, const std::vector<uintptr_t>& mask, const std::vector<uintptr_t>& err,
+         const std::vector<uintptr_t>& partials, const std::vector<int64_t>& L, const std::vector<int32_t>& trunc_len,
+         const std::vector<bool>& aligned, uintptr_t tabs, int parts, uintptr_t part_acc, int src_dt, int dst_dt,
+         double pad, uintptr_t stream, bool dry_run) {
+        const char* what = "launch_var_span_group";
+        const std::string w(what);
+        const size_t nb = out.size();
+        if (nb < 1 || nb > size_t(kMaxGroup)) throw std::invalid_argument(w + ": 1..kMaxGroup batches");
+        for (size_t sz : {rows.size(), slot.size(), lengths.size(), mask.size(), err.size(), partials.size(), L.size(),
+                          trunc_len.size(), aligned.size()})
+          if (sz != nb) throw std::invalid_argument(w + ": one entry per batch in every sequence");
+        if (parts > 1 && part_acc % 8 != 0) throw std::invalid_argument(w + ": part_acc must be 8-byte aligned");
+        VarSpanLaunch a{};
+        a.n_seg = fill_span_segs(a.s, what, nb, src, log_pos, len, flags, crc, row_begin, row_end, batch, seg);
+        const int ssz = dtype_size(src_dt), dsz = dtype_size(dst_dt);
+        const int64_t gbytes = ssz > 0 ? int64_t(16 / ssz) * dsz : 0;
+        for (size_t k = 0; k < nb; ++k) {
+          if (L[k] < 0) throw std::invalid_argument(w + ": negative L");
+          // the aligned path: MainDriver::launch_var_span's condition
+          const bool ok = gbytes >= 16 && gbytes % 16 == 0 && out[k] % 16 == 0 && (L[k] * dsz) % 16 == 0;
+          if (aligned[k] && !ok)
+            throw std::invalid_argument(w + ": the aligned path needs 16-byte groups and 16-byte aligned rows");
+          if (lengths[k] % 8 != 0 || rows[k] % 8 != 0) throw std::invalid_argument(w + ": misaligned rows / lengths");
+          VarSpanBatch& b = a.b[k];
+          b.out = ptr<void>(out[k]);
+          b.rows = ptr<const tk::JsonSpanRow>(rows[k]);
+          b.slot = ptr<const uint8_t>(slot[k]);
+          b.lengths = ptr<int64_t>(lengths[k]);
+          b.mask = ptr<uint8_t>(mask[k]);
+          b.err = ptr<int32_t>(err[k]);
+          b.partials = ptr<uint32_t>(partials[k]);
+          b.L = L[k];
+          b.trunc_len = trunc_len[k];
+          b.reserved = aligned[k] ? 1 : 0;
+        }
+        a.tabs = ptr<const uint32_t>(tabs);
+        a.parts = parts;
+        a.part_acc = ptr<uint32_t>(part_acc);
+        check_var_span(a, src_dt, dst_dt);
+        if (!dry_run) launch_var_span(a, src_dt, dst_dt, pad, stream_of(stream));
+      },
+      py::arg("src"), py::arg("log_pos"), py::arg("len"), py::arg("flags"), py::arg("crc"), py::arg("row_begin"),
+      py::arg("row_end"), py::arg("batch"), py::arg("seg"), py::arg("out"), py::arg("rows"), py::arg("slot"),
+      py::arg("lengths"), py::arg("mask"), py::arg("err"), py::arg("partials"), py::arg("L"), py::arg("trunc_len"),
+      py::arg("aligned"), py::arg("tabs"), py::arg("parts") = 1, py::arg("part_acc") = 0,
+      py::arg("src_dtype") = int(kI32), py::arg("dst_dtype") = int(kI64), py::arg("pad") = 0.0, py::arg("stream") = 0,
+      py::arg("dry_run") = false);
 
   py::class_<Engine>(m, "Engine")
       .def(py::init<int, int, size_t, int, int>(), py::arg("device"), py::arg("n_slots"), py::arg("staging_bytes"),

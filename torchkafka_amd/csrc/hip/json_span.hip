@@ -179,7 +179,7 @@ __global__ __launch_bounds__(kBlock) void json_stage_kernel(JsonStageLaunch a) {
       span::crc_finish(wcrc, flags, sg.crc, sg.seg, bo.err, bo.partials, P, pt.q,
                        a.part_acc + 2 * pt.seg);
   }
-  if (t == 0 && bad) *bo.err = int32_t(sg.seg);  // never committed (reported as this segment)
+  if (t == 0 && bad) span::report_bad_segment(bo.err, sg.seg);  // never committed (reported as this segment)
 }
 
 // Device counting, between the stage and the parse: a wave per device-counted row (a block of four

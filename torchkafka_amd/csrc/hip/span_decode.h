@@ -29,7 +29,7 @@ struct SpanDevSeg {
 struct SpanBatchOut {
   void* out;                 // [rows, row_elems] output of the batch
   const uint64_t* row_pos;   // device view of the slot's row table (log positions of the values)
-  int32_t* err;              // host-mapped status word: -1 clean, else the first bad segment
+  int32_t* err;              // host-mapped status word: -1 clean, else the lowest bad segment
   uint32_t* partials;        // host-mapped raw CRC per segment (RecordBatches spanning segments)
   // Record fields beside the values (key / timestamp, one int64 per row each): the workgroup of
   // the batch's first segment copies ext_words of them from the slot (ext_src; the driver gives
@@ -61,7 +61,7 @@ struct JsonStageBatch {
   const uint8_t* slot;          // device view of the slot payload (the worker-parsed rows' float32 values)
   JsonRowDesc* desc;            // [rows] descriptors for json_rows_kernel (HBM)
   uint8_t* stage;               // the batch's staging area (HBM): texts / float32 values at desc[r].off
-  int32_t* err;                 // host-mapped status word: -1 clean, else the first bad segment (CRC)
+  int32_t* err;                 // host-mapped status word: -1 clean, else the lowest bad segment (CRC)
   uint32_t* partials;           // host-mapped raw CRC per segment (RecordBatches spanning segments)
   int32_t trunc_len;            // rows with more elements keep this many (-1: no limit)
   uint32_t ctr_tag;             // this launch's tag of the ctr words
@@ -92,7 +92,7 @@ struct VarSpanBatch {
   const uint8_t* slot;          // device view of the slot payload (rows the worker copied)
   int64_t* lengths;             // [rows] elements per row (may be null)
   uint8_t* mask;                // [rows, L] (may be null)
-  int32_t* err;                 // host-mapped status word (-1 clean, else the first bad segment)
+  int32_t* err;                 // host-mapped status word (-1 clean, else the lowest bad segment)
   uint32_t* partials;           // host-mapped raw CRC per segment
   int64_t L;
   int32_t trunc_len;            // rows with more elements keep this many (-1: no limit)
@@ -109,6 +109,9 @@ struct VarSpanLaunch {
 };
 
 void launch_var_span(const VarSpanLaunch& a, int src_dt, int dst_dt, double pad, hipStream_t stream);
+// What launch_var_span refuses (std::invalid_argument), without launching: segment lengths and row
+// counts, parts, dtypes, and the addresses the segments' flags make the kernel use.
+void check_var_span(const VarSpanLaunch& a, int src_dt, int dst_dt);
 void prewarm_json_span_kernels();
 
 // Queries the attributes of the span kernel instantiations (loads their code object), so the
@@ -117,6 +120,9 @@ void prewarm_span_kernels(int device);
 
 void launch_span_decode(const SpanLaunch& a, int src_dt, int dst_dt, const float* shift, const float* scale,
                         hipStream_t stream);
+
+// What launch_span_decode refuses (std::invalid_argument), without launching.
+void check_span_decode(const SpanLaunch& a, int src_dt, int dst_dt, const float* shift, const float* scale);
 
 // Validates SpanLaunch::parts (1, 2, 4, 8; accumulator words needed past 1); returns it (0 -> 1).
 int check_parts(int parts, const uint32_t* acc, const char* what);

@@ -318,7 +318,7 @@ __global__ __launch_bounds__(kBlock) void varlen_span_kernel(VarSpanLaunch a, D 
       span::crc_finish(wcrc, flags, sg.crc, sg.seg, bo.err, bo.partials, P, pt.q,
                        a.part_acc + 2 * pt.seg);
   }
-  if (t == 0 && bad) *bo.err = int32_t(sg.seg);
+  if (t == 0 && bad) span::report_bad_segment(bo.err, sg.seg);
 }
 
 template <typename S, typename D>
@@ -357,11 +357,9 @@ void prewarm_span_kernels(int device) {
   (void)hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&span_decode_kernel<float, fp8e4m3, false>));
 }
 
-void launch_var_span(const VarSpanLaunch& a0, int src_dt, int dst_dt, double pad, hipStream_t stream) {
-  VarSpanLaunch a = a0;
-  a.parts = check_parts(a.parts, a.part_acc, "var span");
+void check_var_span(const VarSpanLaunch& a, int src_dt, int dst_dt) {
+  check_parts(a.parts, a.part_acc, "var span");
   if (a.n_seg < 0 || a.n_seg > kMaxLaunchSegs) throw std::invalid_argument("var span: bad segment count");
-  if (a.n_seg == 0) return;
   if (!is_float_dt(dst_dt) && is_float_dt(src_dt))
     throw std::invalid_argument("collate: float records cannot be cast to an integer dtype");
   for (int i = 0; i < a.n_seg; ++i) {
@@ -371,26 +369,51 @@ void launch_var_span(const VarSpanLaunch& a0, int src_dt, int dst_dt, double pad
         s.row_end - s.row_begin > tk::kJsonSpanMaxSegRows || s.batch >= kMaxGroup ||
         (a.b[s.batch].L > 0 && a.b[s.batch].out == nullptr))
       throw std::invalid_argument("var span: malformed segment");
+    const VarSpanBatch& b = a.b[s.batch];
+    // the kernel stores to err (a row table that disagrees, a bad CRC) and reads what its flags name
+    if (b.err == nullptr || (s.row_end > s.row_begin && (b.rows == nullptr || (host && b.slot == nullptr))) ||
+        (!host && (s.flags & tk::kSegCrc) && (a.tabs == nullptr || b.partials == nullptr)))
+      throw std::invalid_argument("var span: a segment without its status word, row table, slot or CRC tables");
   }
+}
+
+void launch_var_span(const VarSpanLaunch& a0, int src_dt, int dst_dt, double pad, hipStream_t stream) {
+  check_var_span(a0, src_dt, dst_dt);
+  VarSpanLaunch a = a0;
+  a.parts = check_parts(a.parts, a.part_acc, "var span");
+  if (a.n_seg == 0) return;
   TK_DISPATCH_SRC(launch_var_span_t, a, pad, stream)
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) throw std::runtime_error(std::string("var span launch: ") + hipGetErrorString(e));
 }
 
-void launch_span_decode(const SpanLaunch& a0, int src_dt, int dst_dt, const float* shift, const float* scale,
-                        hipStream_t stream) {
-  SpanLaunch a = a0;
-  a.parts = check_parts(a.parts, a.part_acc, "span decode");
+void check_span_decode(const SpanLaunch& a, int src_dt, int dst_dt, const float* shift, const float* scale) {
+  check_parts(a.parts, a.part_acc, "span decode");
   if (a.n_seg < 0 || a.n_seg > kMaxLaunchSegs) throw std::invalid_argument("span decode: bad segment count");
   if (!is_float_dt(dst_dt) && is_float_dt(src_dt))
     throw std::invalid_argument("collate: float records cannot be cast to an integer dtype");
   if (shift && !is_float_dt(dst_dt)) throw std::invalid_argument("collate: normalisation needs a float dtype");
+  if ((shift == nullptr) != (scale == nullptr)) throw std::invalid_argument("span decode: shift and scale go together");
+  if (a.n_seg > 0 && a.row_elems < 1) throw std::invalid_argument("span decode: row_elems must be positive");
   for (int i = 0; i < a.n_seg; ++i) {
+    const SpanDevSeg& s = a.s[i];
     // the kernel streams a segment of <= kSpanSegMax bytes and keeps its row positions in LDS
-    if (a.s[i].len == 0 || a.s[i].len > tk::kSpanSegMax || a.s[i].row_end < a.s[i].row_begin ||
-        a.s[i].row_end - a.s[i].row_begin > tk::kSpanMaxSegRows || a.s[i].batch >= kMaxGroup)
+    if (s.len == 0 || s.len > tk::kSpanSegMax || s.src == nullptr || s.row_end < s.row_begin ||
+        s.row_end - s.row_begin > tk::kSpanMaxSegRows || s.batch >= kMaxGroup)
       throw std::invalid_argument("span decode: malformed segment");
+    const SpanBatchOut& b = a.b[s.batch];
+    if ((s.row_end > s.row_begin && (b.out == nullptr || b.row_pos == nullptr)) ||
+        ((s.flags & tk::kSegCrc) && (a.tabs == nullptr || b.err == nullptr || b.partials == nullptr)) ||
+        (b.ext_words && (b.ext_out == nullptr || b.ext_src == nullptr)))
+      throw std::invalid_argument("span decode: a segment without its output, row table, status words or CRC tables");
   }
+}
+
+void launch_span_decode(const SpanLaunch& a0, int src_dt, int dst_dt, const float* shift, const float* scale,
+                        hipStream_t stream) {
+  check_span_decode(a0, src_dt, dst_dt, shift, scale);
+  SpanLaunch a = a0;
+  a.parts = check_parts(a.parts, a.part_acc, "span decode");
   TK_DISPATCH_SRC(launch_span_t, a, shift, scale, stream)
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) throw std::runtime_error(std::string("span decode launch: ") + hipGetErrorString(e));

@@ -334,6 +334,21 @@ __device__ __forceinline__ Part part_of(int parts, int32_t nw) {
   return Part{seg, q, tk::span_part_k0(q, parts, nw), tk::span_part_k0(q + 1, parts, nw)};
 }
 
+// A bad segment's index into its batch's status word, which keeps the LOWEST bad segment of the
+// batch however the workgroups finish (one thread, after the windows: the failure path only).
+// The word is -1 while clean -- as unsigned, above every index and every parse-error word
+// (kSpanParseErrBit) -- so the minimum is a compare-and-swap loop on the unsigned word, at system
+// scope: the driver's words are host-mapped.  Should a platform drop atomics to host memory the
+// word still reads clean afterwards; the plain store then keeps the verdict (some bad segment).
+__device__ __forceinline__ void report_bad_segment(int32_t* err, uint32_t seg) {
+  uint32_t* w = reinterpret_cast<uint32_t*>(err);
+  uint32_t cur = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  while (seg < cur && !__hip_atomic_compare_exchange_strong(w, &cur, seg, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                                            __HIP_MEMORY_SCOPE_SYSTEM)) {
+  }
+  if (int32_t(__hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)) < 0) *err = int32_t(seg);
+}
+
 // Thread 0 only, after a barrier that follows crc_merge: the xor of the 8 wave CRCs; with parts,
 // the accumulation above (`acc`: the segment's two words, 8-byte aligned); then the verdict (a
 // RecordBatch held whole) or the raw partial.
@@ -357,7 +372,7 @@ __device__ __forceinline__ void crc_finish(const uint32_t* wcrc, uint32_t flags,
   }
   constexpr uint32_t kWhole = tk::kSegCrcFirst | tk::kSegCrcLast;
   if ((flags & kWhole) == kWhole) {
-    if ((c ^ 0xFFFFFFFFu) != want) *err = int32_t(seg);
+    if ((c ^ 0xFFFFFFFFu) != want) report_bad_segment(err, seg);
   } else {
     partials[seg] = c;
   }
