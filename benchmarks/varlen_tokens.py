@@ -14,7 +14,14 @@ rows back to back, made from the padded batch by one more launch (pack.hip).  Th
 ``padding_fraction``: the share of the padded [rows, W] batches that is padding, 1 - total / (rows * W)
 over the timed steps (summed on the device, read once at the end).
 
-Usage: python benchmarks/varlen_tokens.py [--steps K] [--decode device|host] [--layout padded|packed]
+``--layout binned --seq-len N`` delivers each batch as a BinnedBatch: the rows packed first-fit into
+sequences of N tokens, [bins, N] values with segment and position ids, made from the padded batch by
+two more launches (bin.hip); ``--bins`` bounds the sequences per batch (default: one per row).  The
+JSON line then carries ``fill_fraction``: real tokens / (n_bins * N) over the timed steps, summed on
+the device and read once at the end (``padding_fraction`` is its complement there).
+
+Usage: python benchmarks/varlen_tokens.py [--steps K] [--decode device|host]
+                                          [--layout padded|packed|binned] [--seq-len N] [--bins B]
 """
 import argparse
 import json
@@ -38,7 +45,9 @@ def main():
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--decode", default="auto", choices=["auto", "device", "host"])
     ap.add_argument("--h2d", default="auto", choices=["auto", "dma", "zerocopy"])
-    ap.add_argument("--layout", default="padded", choices=["padded", "packed"])
+    ap.add_argument("--layout", default="padded", choices=["padded", "packed", "binned"])
+    ap.add_argument("--seq-len", type=int, default=2048, help="--layout binned: tokens per sequence")
+    ap.add_argument("--bins", type=int, default=None, help="--layout binned: sequences per batch (default: rows)")
     ap.add_argument("--coalesce", type=int, default=None, help="batches per launch (default: the loader's)")
     ap.add_argument("--lockstep", default="off", choices=["off", "rccl"],
                     help="rccl: the per-step RCCL agreement at world 1 (a one-rank nccl group), as under DDP")
@@ -74,36 +83,54 @@ def main():
                           decode=args.decode, h2d=args.h2d, lockstep="rccl" if args.lockstep == "rccl" else True,
                           **({"coalesce": args.coalesce} if args.coalesce else {}),
                           **({"layout": "packed"} if args.layout == "packed" else {}),
+                          **({"layout": "binned", "seq_len": args.seq_len, "bins": args.bins}
+                             if args.layout == "binned" else {}),
                           worker_init_fn=Tokens.init_worker("tok", bootstrap_servers=url, group_id="tok",
                                                             auto_offset_reset="earliest"))
-        packed = args.layout == "packed"
+        packed, binned = args.layout == "packed", args.layout == "binned"
         # padding_fraction: the real (non-padding) elements are summed on the device -- `lengths` (padded) or
         # `total` (packed) of 64 steps at a time, three small launches per 64 steps -- and read once after the
         # timed loop.  The warm-up folds too: the first call of a torch kernel loads its code object, which
         # alone costs about as much as the whole timed window.
+        # binned: `bin_lens` the same way, and `n_bins` beside it for fill_fraction.
         real = torch.zeros((), dtype=torch.int64, device=args.device)
-        held = []
+        used = torch.zeros((), dtype=torch.int64, device=args.device)
+        held, held_bins = [], []
 
         def fold():
             real.add_((torch.stack(held) if packed else torch.cat(held)).sum())
             held.clear()
+            if held_bins:
+                used.add_(torch.stack(held_bins).sum())
+                held_bins.clear()
+
+        def hold(item):
+            if binned:
+                held.append(item.bin_lens)
+                held_bins.append(item.n_bins)
+            else:
+                held.append(item.total if packed else item[1])
 
         it = iter(auto_commit(dl))
         for _ in range(args.warmup):
-            item = next(it)
-            held.append(item.total if packed else item[1])
+            hold(next(it))
         if held:
             fold()
         mirror_on = bool(getattr(dl._run, "mirror", False))
         transport = dict(dl.lockstep_info).get("transport")
         real.zero_()
+        used.zero_()
         torch.cuda.synchronize()
         dl.reset_stats()
         t0 = time.perf_counter()
         rows = cells = 0
         for _ in range(args.steps):
             item = next(it)
-            if packed:
+            if binned:
+                x = item.values
+                rows += item.row_bin.shape[0]
+                hold(item)
+            elif packed:
                 x = item.values
                 rows += item.cu_seqlens.shape[0] - 1  # cells: the default capacity is rows * W
                 held.append(item.total)
@@ -118,7 +145,8 @@ def main():
             fold()
         torch.cuda.synchronize()
         el = time.perf_counter() - t0
-        padding = 1.0 - int(real) / max(1, cells)
+        fill = int(real) / max(1, int(used) * args.seq_len) if binned else None
+        padding = 1.0 - (fill if binned else int(real) / max(1, cells))
         st = dl.stats_summary()
         decode = (("device (varlen_span_kernel from an HBM mirror filled by SDMA copies)" if mirror_on
                    else "device (varlen_span_kernel from the pinned logs)") if dl.plan.var_span else "host workers")
@@ -129,6 +157,8 @@ def main():
         rec_bytes = b.partition_stats("tok", 0)["log_bytes"] / max(1, b.end_offset("tok", 0))
         print(json.dumps({"metric": f"int32 token records/s to GPU (int64 {args.layout}), per-batch commit",
                           "layout": args.layout, "padding_fraction": round(padding, 4),
+                          **({"fill_fraction": round(fill, 4), "seq_len": args.seq_len, "bins": args.bins}
+                             if binned else {}),
                           "value": round(rows / el), "ms_per_step": round(el / args.steps * 1e3, 4),
                           "timed_s": round(el, 4), "steps": args.steps, "batch_size": B, "workers": args.workers,
                           "decode": decode, "h2d": args.h2d, "lockstep": transport,

@@ -10,14 +10,14 @@ import numpy.random  # noqa: F401  -- import eagerly: a lazy import racing a Dat
 from .config import LoaderConfig, Tuning
 from .loader import DeviceLoader, KafkaBatch, auto_commit
 from .models import FixedWidth, JsonArray, KafkaDataset, Key, Timestamp, VarLen, WithFields
-from .ops.collate import PackedBatch, pack_padded, reference_packed
+from .ops.collate import BinnedBatch, PackedBatch, bin_padded, pack_padded, reference_binned, reference_packed
 
 __version__ = "1.2.0+mi355x.7"
 
-__all__ = ["KafkaDataset", "auto_commit", "DeviceLoader", "KafkaBatch", "PackedBatch", "LoaderConfig", "Tuning",
-           "FixedWidth", "VarLen", "JsonArray", "Key", "Timestamp", "WithFields", "SyntheticBroker", "KafkaBridge",
-           "KafkaWireServer", "KafkaConsumer", "KafkaProducer", "TopicPartition", "ConsumerRebalanceListener",
-           "pack_padded", "reference_packed"]
+__all__ = ["KafkaDataset", "auto_commit", "DeviceLoader", "KafkaBatch", "PackedBatch", "BinnedBatch", "LoaderConfig",
+           "Tuning", "FixedWidth", "VarLen", "JsonArray", "Key", "Timestamp", "WithFields", "SyntheticBroker",
+           "KafkaBridge", "KafkaWireServer", "KafkaConsumer", "KafkaProducer", "TopicPartition",
+           "ConsumerRebalanceListener", "pack_padded", "reference_packed", "bin_padded", "reference_binned"]
 
 
 def __getattr__(name):

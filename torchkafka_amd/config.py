@@ -196,10 +196,11 @@ _CHOICES = {
     "decode": ("auto", "device", "host"),
     "json_parse": ("auto", "device", "host"),
     "multiprocessing_context": ("fork", "spawn", "forkserver"),
-    "layout": ("padded", "packed"),
+    "layout": ("padded", "packed", "binned"),
 }
 _CHOICE_HELP = {
-    "layout": "'padded' ([rows, width] + lengths) or 'packed' (flat values + cu_seqlens, a PackedBatch)",
+    "layout": ("'padded' ([rows, width] + lengths), 'packed' (flat values + cu_seqlens, a PackedBatch) or "
+               "'binned' (rows packed first-fit into [bins, seq_len] sequences, a BinnedBatch)"),
     "h2d": "'auto', 'dma' (hipMemcpyAsync on side streams), 'zerocopy' or 'direct'",
     "decode": "'auto', 'device' (gfx950 RecordBatch decode) or 'host' (worker pack)",
     "json_parse": "'auto', 'device' (gfx950 parse kernel) or 'host' (worker parse)",
@@ -229,6 +230,8 @@ class LoaderConfig:
     layout: str = "padded"
     pack_to: Optional[int] = None
     return_ids: bool = False
+    seq_len: Optional[int] = None
+    bins: Optional[int] = None
     return_info: bool = False
     native: bool = True
     multiprocessing_context: str = "fork"
@@ -270,6 +273,13 @@ class LoaderConfig:
         _check(packed or self.pack_to is None, "pack_to needs layout='packed'")
         _check(packed or not self.return_ids, "return_ids needs layout='packed'")
         _check(self.pack_to is None or 1 <= int(self.pack_to) < 1 << 31, "pack_to must be in [1, 2^31) (or None)")
+        binned = self.layout == "binned"
+        _check(not (binned and self.return_mask), "layout='binned' has no mask: return_mask=True needs layout='padded'")
+        _check(binned or self.seq_len is None, "seq_len needs layout='binned'")
+        _check(binned or self.bins is None, "bins needs layout='binned'")
+        _check(not binned or (self.seq_len is not None and 1 <= int(self.seq_len) < 1 << 31),
+               "layout='binned' needs seq_len in [1, 2^31)")
+        _check(self.bins is None or 1 <= int(self.bins) <= 16384, "bins must be in [1, 16384] (or None)")
         _check(float(self.timeout) >= 0, "timeout must be >= 0 (0 waits forever)")
         _check(self.rank is None or int(self.rank) >= 0, "rank must be >= 0")
         _check(self.world_size is None or int(self.world_size) >= 1, "world_size must be >= 1")

@@ -155,6 +155,24 @@ PYBIND11_MODULE(_tkhip, m) {
       py::arg("capacity"), py::arg("pad_bits") = 0, py::arg("cu_seqlens") = 0, py::arg("total") = 0,
       py::arg("position_ids") = 0, py::arg("segment_ids") = 0, py::arg("stream") = 0);
 
+  m.attr("BIN_MAX_ROWS") = kBinMaxRows;
+  m.def(
+      "bin_rows",
+      [](uintptr_t padded, int elem_size, int64_t rows, int64_t W, uintptr_t lengths, int64_t seq_len, int64_t bins,
+         uintptr_t values, uint64_t pad_bits, uintptr_t seg, uintptr_t pos, uintptr_t bin_lens, uintptr_t row_bin,
+         uintptr_t row_start, uintptr_t row_lens, uintptr_t n_bins, uintptr_t unplaced, uintptr_t cut,
+         uintptr_t stream) {
+        launch_bin_rows(ptr<const void>(padded), elem_size, rows, W, ptr<const int64_t>(lengths), seq_len, bins,
+                        ptr<void>(values), pad_bits, ptr<int32_t>(seg), ptr<int32_t>(pos), ptr<int32_t>(bin_lens),
+                        ptr<int32_t>(row_bin), ptr<int32_t>(row_start), ptr<int32_t>(row_lens), ptr<int32_t>(n_bins),
+                        ptr<int32_t>(unplaced), ptr<int64_t>(cut), stream_of(stream));
+      },
+      py::arg("padded"), py::arg("elem_size"), py::arg("rows"), py::arg("W"), py::arg("lengths"), py::arg("seq_len"),
+      py::arg("bins"), py::arg("values"), py::arg("pad_bits") = 0, py::arg("segment_ids") = 0,
+      py::arg("position_ids") = 0, py::arg("bin_lens") = 0, py::arg("row_bin") = 0, py::arg("row_start") = 0,
+      py::arg("row_lens") = 0, py::arg("n_bins") = 0, py::arg("unplaced") = 0, py::arg("cut") = 0,
+      py::arg("stream") = 0);
+
   m.def(
       "launch_json_rows",
       [](uintptr_t rows, uintptr_t vals, uintptr_t out, int dst_dt, int64_t n_rows, int64_t L, double pad,

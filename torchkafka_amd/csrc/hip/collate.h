@@ -88,6 +88,18 @@ void launch_pack_rows(const void* padded, int elem_size, int64_t rows, int64_t W
                       int64_t capacity, uint64_t pad_bits, int32_t* cu, int64_t* total, int32_t* pos, int32_t* seg,
                       hipStream_t stream);
 
+// Padded [rows, W] + int64 lengths[rows] -> the binned layout (bin.hip): rows placed first-fit, in
+// arrival order, into `bins` sequences of `seq_len` elements.  values / seg / pos are [bins, seq_len]
+// (`pad_bits` / -1 / 0 where no row landed), int32 bin_lens[bins], row_bin / row_start / row_lens
+// [rows] (-1 / -1 for a row that found no bin), *n_bins, *unplaced and the int64 *cut (elements of
+// rows longer than seq_len).  Two launches: a one-workgroup plan (free[] in LDS, hence kBinMaxRows)
+// and the move.
+constexpr int kBinMaxRows = 16384;
+void launch_bin_rows(const void* padded, int elem_size, int64_t rows, int64_t W, const int64_t* lengths,
+                     int64_t seq_len, int64_t bins, void* values, uint64_t pad_bits, int32_t* seg, int32_t* pos,
+                     int32_t* bin_lens, int32_t* row_bin, int32_t* row_start, int32_t* row_lens, int32_t* n_bins,
+                     int32_t* unplaced, int64_t* cut, hipStream_t stream);
+
 std::vector<std::pair<std::string, double>> api_bench(int device, int iters);
 
 }  // namespace tkh

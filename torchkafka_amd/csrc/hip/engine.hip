@@ -308,7 +308,12 @@ uint32_t* Engine::part_acc(hipStream_t stream) {
   const size_t bytes = kSetWords * kPartAccSets * sizeof(uint32_t);
   TKH_CHECK(hipSetDevice(device_));
   TKH_CHECK(hipMalloc(reinterpret_cast<void**>(&p), bytes));
-  TKH_CHECK(hipMemset(p, 0, bytes));
+  // Zeroed ON `stream`, in order with the launches that use the words (through the command queue
+  // when the stream's calls go there).  A hipMemset runs on the null stream, which a non-blocking
+  // decode stream does not wait for, and HIP does not promise that a fill of device memory has
+  // finished when the call returns: behind work queued on the null stream it could land after the
+  // first split launch, which then merged its parts into whatever a recycled allocation held.
+  run_on(stream, [p, bytes, stream] { TKH_CHECK(hipMemsetAsync(p, 0, bytes, stream)); });
   part_acc_.push_back(PartAcc{stream, p, 1});
   return p;
 }

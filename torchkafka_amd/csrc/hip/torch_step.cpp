@@ -670,6 +670,51 @@ void register_torch_step(py::module_& m) {
       "-> (values [capacity], cu_seqlens int32 [rows + 1], total int64 []"
       "[, position_ids, segment_ids int32 [capacity]]), launched on the current stream");
 
+  // Padded [rows, W] + int64 lengths -> the binned layout (bin.hip), outputs allocated here on the
+  // current stream, as pack_tensors does.  Four allocations: values, the two id planes as one
+  // [2, bins, seq_len] block, the int32 metadata as one block, cut.
+  m.def(
+      "bin_tensors",
+      [](py::handle padded_h, py::handle lengths_h, int64_t seq_len, int64_t bins, uint64_t pad_bits) -> py::tuple {
+        if (!THPVariable_Check(padded_h.ptr()) || !THPVariable_Check(lengths_h.ptr()))
+          throw std::invalid_argument("bin_tensors: padded and lengths must be tensors");
+        const at::Tensor& padded = THPVariable_Unpack(padded_h.ptr());
+        const at::Tensor& lengths = THPVariable_Unpack(lengths_h.ptr());
+        if (!padded.is_cuda() || padded.dim() != 2 || !padded.is_contiguous())
+          throw std::invalid_argument("bin_tensors: padded must be a contiguous [rows, W] device tensor");
+        const int64_t rows = padded.size(0), W = padded.size(1);
+        if (lengths.scalar_type() != at::kLong || lengths.dim() != 1 || lengths.size(0) != rows ||
+            !lengths.is_contiguous() || lengths.device() != padded.device())
+          throw std::invalid_argument("bin_tensors: lengths must be contiguous int64 [rows] on padded's device");
+        if (seq_len < 1 || bins < 0 || bins > kBinMaxRows || rows > kBinMaxRows ||
+            seq_len >= (int64_t(1) << 31) || bins * seq_len >= (int64_t(1) << 31))
+          throw std::invalid_argument("bin_tensors: seq_len >= 1, rows and bins <= " + std::to_string(kBinMaxRows) +
+                                      ", bins * seq_len < 2^31");
+        const auto dev = padded.device().index();
+        hipStream_t stream = c10::hip::getCurrentHIPStream(dev).stream();
+        const auto opts = padded.options();
+        at::Tensor values = at::empty({bins, seq_len}, opts);
+        at::Tensor ids = at::empty({2, bins, seq_len}, opts.dtype(at::kInt));
+        at::Tensor meta = at::empty({bins + 3 * rows + 2}, opts.dtype(at::kInt));
+        at::Tensor cut = at::empty({}, opts.dtype(at::kLong));
+        int32_t* mp = meta.data_ptr<int32_t>();
+        int32_t* ip = ids.data_ptr<int32_t>();
+        launch_bin_rows(padded.data_ptr(), int(padded.element_size()), rows, W, lengths.data_ptr<int64_t>(), seq_len,
+                        bins, values.data_ptr(), pad_bits, ip, ip + bins * seq_len, mp, mp + bins, mp + bins + rows,
+                        mp + bins + 2 * rows, mp + bins + 3 * rows, mp + bins + 3 * rows + 1,
+                        cut.data_ptr<int64_t>(), stream);
+        auto wrap = [](at::Tensor t) { return py::reinterpret_steal<py::object>(THPVariable_Wrap(std::move(t))); };
+        return py::make_tuple(wrap(std::move(values)), wrap(ids.select(0, 0)), wrap(ids.select(0, 1)),
+                              wrap(meta.narrow(0, 0, bins)), wrap(meta.narrow(0, bins, rows)),
+                              wrap(meta.narrow(0, bins + rows, rows)), wrap(meta.narrow(0, bins + 2 * rows, rows)),
+                              wrap(meta.select(0, bins + 3 * rows)), wrap(meta.select(0, bins + 3 * rows + 1)),
+                              wrap(std::move(cut)));
+      },
+      py::arg("padded"), py::arg("lengths"), py::arg("seq_len"), py::arg("bins"), py::arg("pad_bits") = 0,
+      "-> (values [bins, seq_len], segment_ids, position_ids int32 [bins, seq_len], bin_lens int32 [bins], "
+      "row_bin, row_start, row_lens int32 [rows], n_bins, unplaced int32 [], cut int64 []), launched on the "
+      "current stream");
+
   // Coalesced variant: when several fixed-width batches are already staged, one allocation and
   // one kernel launch serve up to driver.coalesce of them; the following calls return the
   // pre-collated tensors without any HIP call (MainDriver::step_group_begin/launch).

@@ -37,8 +37,8 @@ import torch
 
 from ..client.errors import CorruptRecordException
 from ..config import LoaderConfig
-from ..ops.collate import (CODE_DTYPE, DTYPE_CODE, FLOAT_DTYPES, PackedBatch, _stream_ptr, normalize_params,
-                           pack_launch, pad_bits, reference_packed)
+from ..ops.collate import (CODE_DTYPE, DTYPE_CODE, FLOAT_DTYPES, BinnedBatch, PackedBatch, _stream_ptr, bin_launch,
+                           normalize_params, pack_launch, pad_bits, reference_binned, reference_packed)
 from ..ops.native import core, hip
 from ..parallel.sharding import dist_rank_world
 from ..utils.metrics import LoaderStats
@@ -65,7 +65,7 @@ def _traced_step(step):
 class KafkaBatch(NamedTuple):
     """Batch plus provenance (``return_info=True``)."""
 
-    data: torch.Tensor    # layout="packed": a PackedBatch (lengths and mask are then None)
+    data: torch.Tensor    # layout="packed" / "binned": a PackedBatch / BinnedBatch (lengths and mask are then None)
     lengths: torch.Tensor | None
     mask: torch.Tensor | None
     watermarks: list      # [(pidx, first_offset, next_offset, n_records)]
@@ -116,11 +116,24 @@ class DeviceLoader(LoaderBridges, LoaderCommits, LoaderLockstep):
             device ``total`` -- made from the padded batch by one more gfx950 launch (csrc/hip/pack.hip).
             ``pad_to``, ``pad_multiple``, ``pad_value``, ``dtype`` and the schema's ``max_len`` / ``truncate``
             keep their meaning; there is no mask.  Fixed-width and structured schemas raise ``TypeError``.
+            ``"binned"``: several rows packed into each fixed-length sequence, see ``seq_len``.
         pack_to: ``layout="packed"``: the capacity of every batch's ``values`` (static shapes with
             ``drop_last=True``, e.g. for graph capture).  Rows beyond it are cut: ``cu_seqlens`` is clamped to it
             and ``total > pack_to`` shows the overflow, without a sync.  None: ``rows * width``, nothing is ever cut.
         return_ids: ``layout="packed"``: also int32 ``position_ids`` / ``segment_ids`` ``[capacity]`` (index inside
             the row / row index; 0 / -1 behind the last row).
+        seq_len: ``layout="binned"`` (required there): each batch is a :class:`~torchkafka_amd.BinnedBatch` --
+            ``values[bins, seq_len]`` with several rows packed into each fixed-length sequence, first-fit in arrival
+            order, int32 ``segment_ids`` / ``position_ids`` of the same shape (row index / index inside the row;
+            -1 / 0 in padding), ``bin_lens``, ``row_bin`` / ``row_start`` / ``row_lens`` and the 0-dim device
+            ``n_bins`` / ``unplaced`` / ``cut`` -- made from the padded batch by two more gfx950 launches
+            (csrc/hip/bin.hip).  A row longer than ``seq_len`` is cut there (``cut`` counts the elements lost).
+            The padded-batch options keep their meaning, as for ``"packed"``; there is no mask.
+        bins: ``layout="binned"``: the number of sequences of every batch (static shapes with ``drop_last=True``).
+            None: one per row, so every row finds a bin.  With fewer, a row that fits no bin is left out
+            (``row_bin == -1``, counted in ``unplaced``; later rows may still fit).  Such rows, and cut ones, are
+            still committed with their batch -- exactly as ``pack_to`` treats an overflow; nothing is carried over
+            into the next batch.  At most 16384 rows and bins per batch on the GPU.
         drop_last: drop a final batch shorter than ``batch_size`` (DataLoader's meaning).
         return_info: yield ``(batch, BatchInfo)`` with each batch's partitions and offset ranges.
         native: use the native step driver (``False``: the Python loop, for debugging).
@@ -239,6 +252,11 @@ class DeviceLoader(LoaderBridges, LoaderCommits, LoaderLockstep):
         self.return_ids = bool(cfg.return_ids)
         if self.layout == "packed" and getattr(self.schema, "kind", None) not in (1, 2):
             raise TypeError("layout='packed' needs a VarLen or JsonArray schema (fixed-width and structured "
+                            "samples have no row lengths to pack)")
+        self.seq_len = None if cfg.seq_len is None else int(cfg.seq_len)
+        self.bins = None if cfg.bins is None else int(cfg.bins)
+        if self.layout == "binned" and getattr(self.schema, "kind", None) not in (1, 2):
+            raise TypeError("layout='binned' needs a VarLen or JsonArray schema (fixed-width and structured "
                             "samples have no row lengths to pack)")
         self._pad_bits: dict = {}
         self.return_info = cfg.return_info
@@ -661,16 +679,16 @@ class DeviceLoader(LoaderBridges, LoaderCommits, LoaderLockstep):
         drv.configure_varlen(self.device.index, DTYPE_CODE[dst_dt], -1 if self.pad_to is None else int(self.pad_to),
                              self.pad_multiple, float(self.pad_value), bool(self.return_mask), native_ac, 100,
                              self.verify == "deliver")
-        if self.layout != "packed":
+        if self.layout == "padded":
             return drv.varlen_fast_next
-        native, pack = drv.varlen_fast_next, self._pack
+        native, relayout = drv.varlen_fast_next, (self._pack if self.layout == "packed" else self._bin)
 
         def step():
             # the native step ordered the current stream behind the decode (wait_group) before it
-            # handed the padded batch out, so the pack kernel goes on that stream right behind it
+            # handed the padded batch out, so the pack / bin kernels go on that stream right behind it
             r, cs, item = native()
             if item is not None:
-                item = pack(item[0], item[1])
+                item = relayout(item[0], item[1])
             return r, cs, item
         return step
 
@@ -793,8 +811,8 @@ class DeviceLoader(LoaderBridges, LoaderCommits, LoaderLockstep):
                 out = out.view(-1)[:n_rows * W].view(n_rows, W)
                 if mask is not None:
                     mask = mask.view(-1)[:n_rows * W].view(n_rows, W)
-        if not fixed and self.layout == "packed":
-            out, lengths = self._pack(out, lengths), None
+        if not fixed and self.layout != "padded":
+            out, lengths = self._relayout(out, lengths), None
         self.stats.record_batch(n_rows, payload_bytes, t1 - t0, time.perf_counter_ns() - t1)
         n_rec = sum(w[3] for w in wms)
         if self.return_info:
@@ -895,8 +913,8 @@ class DeviceLoader(LoaderBridges, LoaderCommits, LoaderLockstep):
                 if mask is not None:
                     mask.copy_(res[2])
                 run.ring.main_release(g)
-        if not fixed and self.layout == "packed":
-            out, lengths = self._pack(out, lengths), None
+        if not fixed and self.layout != "padded":
+            out, lengths = self._relayout(out, lengths), None
         n_rec = sum(w[3] for w in wms)
         if self.return_info:
             return KafkaBatch(out, lengths, mask, wms, n_rec)
@@ -906,9 +924,10 @@ class DeviceLoader(LoaderBridges, LoaderCommits, LoaderLockstep):
             return out
         return (out, lengths, mask) if self.return_mask else (out, lengths)
 
-    def _pack(self, out: torch.Tensor, lengths: torch.Tensor) -> PackedBatch:
-        """A delivered padded batch -> its PackedBatch, by one launch on the current stream (the
-        stream the batch is delivered on; every route has ordered it behind the decode by now).
+    def _relayout(self, out: torch.Tensor, lengths: torch.Tensor) -> PackedBatch | BinnedBatch:
+        """The post-layout step of every var-len route: a delivered padded batch -> the batch in
+        ``self.layout`` ("packed" or "binned"), launched on the current stream (the stream the batch
+        is delivered on; every route has ordered it behind the decode by now).
 
         The padded tensor and its lengths are dropped when this returns.  That is safe for the same
         reason a user may drop a delivered batch right after launching work on it: a block the
@@ -916,6 +935,23 @@ class DeviceLoader(LoaderBridges, LoaderCommits, LoaderLockstep):
         (torch_step.cpp alloc_group / alloc_json_group: recordStream), so the caching allocator
         hands it out again only after an event behind this launch; every other route allocates on
         the delivery stream itself, where reuse is ordered behind the launch by the stream."""
+        return self._pack(out, lengths) if self.layout == "packed" else self._bin(out, lengths)
+
+    def _bin(self, out: torch.Tensor, lengths: torch.Tensor) -> BinnedBatch:
+        """A delivered padded batch -> its BinnedBatch (two launches, csrc/hip/bin.hip)."""
+        rows, W = out.shape
+        bins = rows if self.bins is None else self.bins
+        if out.device.type != "cuda":
+            return reference_binned(out, lengths, self.seq_len, bins, self.pad_value)
+        if rows * W >= 1 << 31 or bins * self.seq_len >= 1 << 31:
+            raise ValueError("layout='binned': rows * width and bins * seq_len must be below 2^31")
+        bits = self._pad_bits.get(out.dtype)
+        if bits is None:
+            bits = self._pad_bits[out.dtype] = pad_bits(out.dtype, self.pad_value)
+        return bin_launch(out, lengths, self.seq_len, bins, bits)  # above hip().BIN_MAX_ROWS rows: ValueError
+
+    def _pack(self, out: torch.Tensor, lengths: torch.Tensor) -> PackedBatch:
+        """A delivered padded batch -> its PackedBatch, by one launch (csrc/hip/pack.hip)."""
         rows, W = out.shape
         cap = rows * W if self.pack_to is None else self.pack_to
         if out.device.type != "cuda":

@@ -175,6 +175,94 @@ def pack_padded(padded: torch.Tensor, lengths: torch.Tensor, capacity: int | Non
     return pack_launch(padded.contiguous(), lengths, cap, pad_bits(padded.dtype, pad_value), return_ids)
 
 
+# ----------------------------------------------------------------------------- binned (first-fit) layout
+class BinnedBatch(NamedTuple):
+    """A var-len batch with several rows packed into each fixed-length sequence (``layout="binned"``).
+
+    Rows are placed first-fit in arrival order: row ``r`` goes to the lowest of the ``bins`` sequences
+    that still has room for it and lies at ``values[row_bin[r], row_start[r]:row_start[r] + row_lens[r]]``.
+    A row longer than ``seq_len`` is cut there; a row that fits no bin is left out (``row_bin == -1``).
+    The bins in use are a prefix, ``[0, n_bins)``.
+
+    Fields:
+        values: ``[bins, seq_len]`` in the output dtype, the pad value where no row landed.
+        segment_ids: int32 ``[bins, seq_len]``: the row's index within the batch, -1 in padding.
+        position_ids: int32 ``[bins, seq_len]``: ``i`` for element ``i`` of its row, 0 in padding.
+        bin_lens: int32 ``[bins]``, the elements placed in each bin.
+        row_bin, row_start: int32 ``[rows]``, where each row went (-1 / -1: it fitted no bin).
+        row_lens: int32 ``[rows]``, each row's length after the cut at ``seq_len``.
+        n_bins: 0-dim int32 device tensor, the number of bins holding an element.
+        unplaced: 0-dim int32 device tensor, the rows that fitted no bin.
+        cut: 0-dim int64 device tensor, the elements cut off rows longer than ``seq_len``.
+            ``unplaced > 0`` or ``cut > 0`` shows an overflow; reading them synchronises, so the
+            loader never does.
+        seq_len: the length of every sequence (a Python int).
+
+    On the GPU ``segment_ids`` / ``position_ids`` are the two planes of one allocation, and the int32
+    metadata tensors are slices of another.
+    """
+
+    values: torch.Tensor
+    segment_ids: torch.Tensor
+    position_ids: torch.Tensor
+    bin_lens: torch.Tensor
+    row_bin: torch.Tensor
+    row_start: torch.Tensor
+    row_lens: torch.Tensor
+    n_bins: torch.Tensor
+    unplaced: torch.Tensor
+    cut: torch.Tensor
+    seq_len: int
+
+    def trim(self) -> "BinnedBatch":
+        """The batch restricted to the bins in use: ``values``, ``segment_ids``, ``position_ids`` and
+        ``bin_lens`` cut to ``[:n_bins]``.  SYNCHRONISES with the device (it reads ``n_bins``); keep
+        the full ``[bins, seq_len]`` tensors where shapes must stay static."""
+        k = int(self.n_bins.item())
+        return self._replace(values=self.values[:k], segment_ids=self.segment_ids[:k],
+                             position_ids=self.position_ids[:k], bin_lens=self.bin_lens[:k])
+
+
+def _bin_shape(padded: torch.Tensor, lengths: torch.Tensor, seq_len, bins) -> tuple[int, int, int, int]:
+    if padded.dim() != 2:
+        raise ValueError("bin: padded must be [rows, width]")
+    rows, W = padded.shape
+    if lengths.dim() != 1 or lengths.numel() != rows:
+        raise ValueError("bin: lengths must be [rows]")
+    if padded.element_size() not in _BITS_VIEW:
+        raise TypeError(f"bin: unsupported dtype {padded.dtype}")
+    seq_len = int(seq_len)
+    bins = rows if bins is None else int(bins)
+    if seq_len < 1 or bins < 0:
+        raise ValueError("bin: seq_len must be >= 1 and bins >= 0")
+    if seq_len >= _PACK_LIMIT or bins * seq_len >= _PACK_LIMIT or rows * W >= _PACK_LIMIT:
+        raise ValueError("bin: rows * width and bins * seq_len must be below 2^31")
+    return rows, W, seq_len, bins
+
+
+def bin_launch(padded: torch.Tensor, lengths: torch.Tensor, seq_len: int, bins: int, bits: int) -> BinnedBatch:
+    """The bin kernels on the current stream; ``padded`` contiguous ``[rows, W]`` on the GPU,
+    ``lengths`` contiguous int64, ``bits`` from :func:`pad_bits` (the loader's per-batch entry)."""
+    return BinnedBatch(*hip().bin_tensors(padded, lengths, seq_len, bins, bits), seq_len)
+
+
+def bin_padded(padded: torch.Tensor, lengths: torch.Tensor, seq_len: int, bins: int | None = None,
+               pad_value: float = 0) -> BinnedBatch:
+    """Padded ``[rows, W]`` + ``lengths`` [rows] -> :class:`BinnedBatch` of ``bins`` sequences of
+    ``seq_len`` elements (default ``bins = rows``: every row finds a bin), rows placed first-fit in
+    arrival order, in two gfx950 launches on the current stream.  A length below 0 counts as 0, one
+    above ``W`` as ``W``.  ``rows`` and ``bins`` may be at most ``hip().BIN_MAX_ROWS`` on the GPU
+    (``ValueError`` above); CPU tensors take :func:`reference_binned`, which has no such limit."""
+    if padded.device.type != "cuda":
+        return reference_binned(padded, lengths, seq_len, bins, pad_value)
+    rows, W, seq_len, bins = _bin_shape(padded, lengths, seq_len, bins)
+    limit = int(hip().BIN_MAX_ROWS)
+    if rows > limit or bins > limit:
+        raise ValueError(f"bin: the device path takes at most {limit} rows and bins")
+    lengths = lengths.to(device=padded.device, dtype=torch.int64).contiguous()
+    return bin_launch(padded.contiguous(), lengths, seq_len, bins, pad_bits(padded.dtype, pad_value))
+
+
 # ----------------------------------------------------------------------------- torch references
 def reference_fixed(src: torch.Tensor, dtype: torch.dtype, normalize=None) -> torch.Tensor:
     if normalize is None:
@@ -237,3 +325,47 @@ def reference_packed(padded: torch.Tensor, lengths: torch.Tensor, capacity: int 
         pos[:kept] = col_idx.to(torch.int32)
         seg[:kept] = row_idx.to(torch.int32)
     return PackedBatch(values.view(padded.dtype), cu.to(torch.int32), W, total, pos, seg)
+
+
+def reference_binned(padded: torch.Tensor, lengths: torch.Tensor, seq_len: int, bins: int | None = None,
+                     pad_value: float = 0) -> BinnedBatch:
+    """:func:`bin_padded` in plain torch (the CPU path; no size limit).  The placement walks the rows
+    in order -- first-fit is sequential -- and searches the bins with one torch op per row; the
+    elements then move in one gather over integer views of the element size, so fp8 values and NaN
+    payloads pass through untouched."""
+    rows, W, seq_len, bins = _bin_shape(padded, lengths, seq_len, bins)
+    dev = padded.device
+    ib = _BITS_VIEW[padded.element_size()]
+    src = padded.contiguous().view(ib)
+    full = lengths.to(device="cpu", dtype=torch.int64).clamp(0, W)
+    lens = full.clamp(max=seq_len)
+    room = torch.full((bins,), seq_len, dtype=torch.int64)
+    row_bin = torch.full((rows,), -1, dtype=torch.int64)
+    row_start = torch.full((rows,), -1, dtype=torch.int64)
+    for r, n in enumerate(lens.tolist()):
+        fits = torch.nonzero(room >= n)
+        if fits.numel():
+            b = int(fits[0])
+            row_bin[r], row_start[r] = b, seq_len - int(room[b])
+            room[b] -= n
+    placed = row_bin >= 0
+    kept_per_row = torch.where(placed, lens, torch.zeros_like(lens))
+    kept = int(kept_per_row.sum())
+    row_idx = torch.repeat_interleave(torch.arange(rows), kept_per_row)
+    col_idx = torch.arange(kept) - torch.repeat_interleave(torch.cumsum(kept_per_row, 0) - kept_per_row, kept_per_row)
+    cell = (row_bin[row_idx] * seq_len + row_start[row_idx] + col_idx).to(dev)
+    row_idx, col_idx = row_idx.to(dev), col_idx.to(dev)
+    values = torch.full((bins * seq_len,), int(pad_fill(padded.dtype, pad_value).view(ib).item()), dtype=ib, device=dev)
+    seg = torch.full((bins * seq_len,), -1, dtype=torch.int32, device=dev)
+    pos = torch.zeros(bins * seq_len, dtype=torch.int32, device=dev)
+    values[cell] = src[row_idx, col_idx]
+    seg[cell] = row_idx.to(torch.int32)
+    pos[cell] = col_idx.to(torch.int32)
+    bin_lens = seq_len - room
+
+    def i32(t):
+        return t.to(device=dev, dtype=torch.int32)
+
+    return BinnedBatch(values.view(padded.dtype).view(bins, seq_len), seg.view(bins, seq_len), pos.view(bins, seq_len),
+                       i32(bin_lens), i32(row_bin), i32(row_start), i32(lens), i32((bin_lens > 0).sum()),
+                       i32((~placed).sum()), (full - lens).sum().to(dev), seq_len)
