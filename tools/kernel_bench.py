@@ -11,7 +11,10 @@ is the wall time per eager call including the Python wrapper and launch.
 ``pack_rows`` (padded -> packed cu_seqlens layout, pack.hip) has no single PyTorch kernel to stand
 beside: a boolean-mask gather synchronises with the host, so it cannot be graph-timed.
 
-Usage: python tools/kernel_bench.py [--quick] [--iters N] [--only pack_rows]
+``mx_quantize`` (f32 / bf16 -> OCP MX blocks, mx_quant.hip) stands beside ``reference_mx``, the
+plain-torch composition of the same rules, running on the same GPU; the two are timed alternately.
+
+Usage: python tools/kernel_bench.py [--quick] [--iters N] [--only pack_rows|mx_quantize]
 """
 import argparse
 import json
@@ -114,11 +117,68 @@ def pack_rows_cases(dev, iters):
     return res
 
 
+HBM_ROOF_GBPS = 6290.0  # measured float4 copy on MI355X (8 TB/s spec)
+
+
+def mx_quantize_cases(dev, iters, rounds=3):
+    """The config-2 batch (f32 [256, 256]), eight of them as one [2048, 256], and a [256, 2048] bf16
+    token-feature batch -> mxfp8 and mxfp4.  ``gpu_us``: device time per launch (graph replay);
+    ``GBps``: (input + values + scales bytes) / time and its share of the measured HBM roof;
+    ``torch_gpu_us``: ``reference_mx`` on the same GPU, graph-replayed too (its launches back to back,
+    no host gaps), the two alternated ``rounds`` times in this call (the median is reported, the
+    spread kept); ``eager_us`` / ``torch_eager_us``: wall time per call with the host's launch cost."""
+    import statistics
+
+    import torch
+
+    from torchkafka_amd.ops.collate import DTYPE_CODE, MX_FORMATS, mx_launch, quantize_mx, reference_mx
+    from torchkafka_amd.ops.native import hip
+
+    mod = hip()
+    g = torch.Generator().manual_seed(2)
+    res = []
+    for name, shape, dt in (("config2 batch 256x256 f32", (256, 256), torch.float32),
+                            ("8 config2 batches 2048x256 f32", (2048, 256), torch.float32),
+                            ("token features 256x2048 bf16", (256, 2048), torch.bfloat16)):
+        x = (torch.randn(shape, generator=g) * torch.exp2(torch.randint(-8, 8, shape, generator=g).float())).to(dt)
+        x = x.to(dev)
+        for fmt, code in MX_FORMATS.items():
+            ours, ref = quantize_mx(x, fmt), reference_mx(x, fmt)
+            assert torch.equal(ours.values.view(torch.uint8), ref.values.view(torch.uint8))
+            assert torch.equal(ours.scales, ref.scales)
+            nbytes = x.numel() * x.element_size() + ours.values.numel() + ours.scales.numel()
+            values, scales = torch.empty_like(ours.values), torch.empty_like(ours.scales)
+
+            def kernel():
+                mod.mx_quantize(x.data_ptr(), DTYPE_CODE[dt], x.numel() // 32, code, values.data_ptr(),
+                                scales.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+
+            kernel()
+            assert torch.equal(values.view(torch.uint8), ref.values.view(torch.uint8))
+            assert torch.equal(scales, ref.scales)
+            t_ours, t_ref = [], []
+            for _ in range(rounds):  # alternated: other work shares the machine
+                t_ours.append(timeit_graph(kernel, iters))
+                t_ref.append(timeit_graph(lambda: reference_mx(x, fmt), iters))
+            g_ours, g_ref = statistics.median(t_ours), statistics.median(t_ref)
+            e_ours = timeit(lambda: quantize_mx(x, fmt), iters)
+            e_ref = timeit(lambda: reference_mx(x, fmt), iters)
+            t_entry = timeit(lambda: mx_launch(x, code, fmt), iters)  # what the loader calls per batch
+            res.append({"kernel": "mx_quantize", "case": f"{name} -> {fmt}", "gpu_us": round(g_ours, 2),
+                        "gpu_us_rounds": [round(t, 2) for t in t_ours], "bytes": nbytes,
+                        "GBps": round(nbytes / g_ours / 1e3, 1),
+                        "hbm_roof_share": round(nbytes / g_ours / 1e3 / HBM_ROOF_GBPS, 4),
+                        "torch_gpu_us": round(g_ref, 2), "torch_gpu_us_rounds": [round(t, 2) for t in t_ref],
+                        "eager_us": round(e_ours, 2), "torch_eager_us": round(e_ref, 2),
+                        "loader_entry_us": round(t_entry, 2)})
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true", help="fewer iterations (for counter collection)")
     ap.add_argument("--iters", type=int, default=200)
-    ap.add_argument("--only", default=None, choices=["pack_rows"], help="run only this kernel's cases")
+    ap.add_argument("--only", default=None, choices=["pack_rows", "mx_quantize"], help="run only this kernel's cases")
     args = ap.parse_args()
     iters = 20 if args.quick else args.iters
 
@@ -131,6 +191,10 @@ def main():
     dev = torch.device("cuda", 0)
     if args.only == "pack_rows":
         for r in pack_rows_cases(dev, iters):
+            print(json.dumps(r))
+        return
+    if args.only == "mx_quantize":
+        for r in mx_quantize_cases(dev, iters):
             print(json.dumps(r))
         return
     out = []
@@ -257,6 +321,7 @@ def main():
                     "host_parser_us_one_core": round(host_us, 1)})
 
     out += pack_rows_cases(dev, iters)
+    out += mx_quantize_cases(dev, iters)
     for r in out:
         print(json.dumps(r))
 

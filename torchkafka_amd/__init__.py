@@ -10,14 +10,16 @@ import numpy.random  # noqa: F401  -- import eagerly: a lazy import racing a Dat
 from .config import LoaderConfig, Tuning
 from .loader import DeviceLoader, KafkaBatch, auto_commit
 from .models import FixedWidth, JsonArray, KafkaDataset, Key, Timestamp, VarLen, WithFields
-from .ops.collate import BinnedBatch, PackedBatch, bin_padded, pack_padded, reference_binned, reference_packed
+from .ops.collate import (BinnedBatch, MXBatch, PackedBatch, bin_padded, pack_padded, quantize_mx, reference_binned,
+                          reference_mx, reference_packed)
 
 __version__ = "1.2.0+mi355x.7"
 
 __all__ = ["KafkaDataset", "auto_commit", "DeviceLoader", "KafkaBatch", "PackedBatch", "BinnedBatch", "LoaderConfig",
            "Tuning", "FixedWidth", "VarLen", "JsonArray", "Key", "Timestamp", "WithFields", "SyntheticBroker",
            "KafkaBridge", "KafkaWireServer", "KafkaConsumer", "KafkaProducer", "TopicPartition",
-           "ConsumerRebalanceListener", "pack_padded", "reference_packed", "bin_padded", "reference_binned"]
+           "ConsumerRebalanceListener", "pack_padded", "reference_packed", "bin_padded", "reference_binned", "MXBatch",
+           "quantize_mx", "reference_mx"]
 
 
 def __getattr__(name):

@@ -197,8 +197,11 @@ _CHOICES = {
     "json_parse": ("auto", "device", "host"),
     "multiprocessing_context": ("fork", "spawn", "forkserver"),
     "layout": ("padded", "packed", "binned"),
+    "quantize": (None, "mxfp8", "mxfp4"),
 }
 _CHOICE_HELP = {
+    "quantize": ("None, 'mxfp8' or 'mxfp4' (the values delivered as an MXBatch: OCP Microscaling blocks of 32 "
+                 "elements with one E8M0 scale each)"),
     "layout": ("'padded' ([rows, width] + lengths), 'packed' (flat values + cu_seqlens, a PackedBatch) or "
                "'binned' (rows packed first-fit into [bins, seq_len] sequences, a BinnedBatch)"),
     "h2d": "'auto', 'dma' (hipMemcpyAsync on side streams), 'zerocopy' or 'direct'",
@@ -232,6 +235,7 @@ class LoaderConfig:
     return_ids: bool = False
     seq_len: Optional[int] = None
     bins: Optional[int] = None
+    quantize: Optional[str] = None
     return_info: bool = False
     native: bool = True
     multiprocessing_context: str = "fork"
@@ -280,6 +284,8 @@ class LoaderConfig:
         _check(not binned or (self.seq_len is not None and 1 <= int(self.seq_len) < 1 << 31),
                "layout='binned' needs seq_len in [1, 2^31)")
         _check(self.bins is None or 1 <= int(self.bins) <= 16384, "bins must be in [1, 16384] (or None)")
+        _check(self.quantize is None or self.layout == "padded",
+               "quantize needs layout='padded' (MX over the packed / binned layouts is not supported)")
         _check(float(self.timeout) >= 0, "timeout must be >= 0 (0 waits forever)")
         _check(self.rank is None or int(self.rank) >= 0, "rank must be >= 0")
         _check(self.world_size is None or int(self.world_size) >= 1, "world_size must be >= 1")

@@ -173,6 +173,16 @@ PYBIND11_MODULE(_tkhip, m) {
       py::arg("row_lens") = 0, py::arg("n_bins") = 0, py::arg("unplaced") = 0, py::arg("cut") = 0,
       py::arg("stream") = 0);
 
+  m.attr("MX_MAX_GRID") = kMxMaxGrid;
+  m.def(
+      "mx_quantize",
+      [](uintptr_t src, int src_dt, int64_t n_blocks, int fmt, uintptr_t values, uintptr_t scales, uintptr_t stream) {
+        launch_mx_quantize(ptr<const void>(src), src_dt, n_blocks, fmt, ptr<void>(values), ptr<uint8_t>(scales),
+                           stream_of(stream));
+      },
+      py::arg("src"), py::arg("src_dtype"), py::arg("n_blocks"), py::arg("fmt"), py::arg("values"), py::arg("scales"),
+      py::arg("stream") = 0);
+
   m.def(
       "launch_json_rows",
       [](uintptr_t rows, uintptr_t vals, uintptr_t out, int dst_dt, int64_t n_rows, int64_t L, double pad,

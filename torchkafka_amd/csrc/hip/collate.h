@@ -100,6 +100,14 @@ void launch_bin_rows(const void* padded, int elem_size, int64_t rows, int64_t W,
                      int32_t* bin_lens, int32_t* row_bin, int32_t* row_start, int32_t* row_lens, int32_t* n_bins,
                      int32_t* unplaced, int64_t* cut, hipStream_t stream);
 
+// A contiguous f32 / bf16 / f16 array of n_blocks * 32 elements (16-byte aligned) -> OCP MX
+// (mx_quant.hip, rules in mx_block.h): `fmt` 0 = mxfp8, values[32 * n_blocks] e4m3fn bytes; 1 = mxfp4,
+// values[16 * n_blocks] with two e2m1 codes per byte (element 2i in the low nibble); scales[n_blocks]
+// E8M0 bytes, plain row-major.  `values` 16-byte aligned.  One launch of at most kMxMaxGrid workgroups.
+constexpr int kMxMaxGrid = 2048;
+void launch_mx_quantize(const void* src, int src_dt, int64_t n_blocks, int fmt, void* values, uint8_t* scales,
+                        hipStream_t stream);
+
 std::vector<std::pair<std::string, double>> api_bench(int device, int iters);
 
 }  // namespace tkh

@@ -715,6 +715,44 @@ void register_torch_step(py::module_& m) {
       "row_bin, row_start, row_lens int32 [rows], n_bins, unplaced int32 [], cut int64 []), launched on the "
       "current stream");
 
+  // A contiguous float tensor -> its OCP MX form (mx_quant.hip), outputs allocated here on the current
+  // stream, as pack_tensors does: values in x's shape (mxfp8, e4m3fn) or with the last dimension
+  // halved (mxfp4, uint8), scales uint8 with the last dimension / 32.
+  m.def(
+      "mx_tensors",
+      [](py::handle x_h, int fmt) -> py::tuple {
+        if (!THPVariable_Check(x_h.ptr())) throw std::invalid_argument("mx_tensors: x must be a tensor");
+        const at::Tensor& x = THPVariable_Unpack(x_h.ptr());
+        if (!x.is_cuda() || x.dim() < 1 || !x.is_contiguous())
+          throw std::invalid_argument("mx_tensors: x must be a contiguous device tensor of at least one dimension");
+        int src_dt;
+        switch (x.scalar_type()) {
+          case at::kFloat: src_dt = kF32; break;
+          case at::kBFloat16: src_dt = kBF16; break;
+          case at::kHalf: src_dt = kF16; break;
+          default: throw std::invalid_argument("mx_tensors: x must be float32, bfloat16 or float16");
+        }
+        if (fmt != 0 && fmt != 1) throw std::invalid_argument("mx_tensors: fmt must be 0 (mxfp8) or 1 (mxfp4)");
+        const int64_t K = x.size(-1), n = x.numel();
+        if (K % 32 != 0 || n >= (int64_t(1) << 31))
+          throw std::invalid_argument("mx_tensors: the last dimension must be a multiple of 32 and numel below 2^31");
+        if (reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 != 0)
+          throw std::invalid_argument("mx_tensors: x must be 16-byte aligned");
+        const auto dev = x.device().index();
+        hipStream_t stream = c10::hip::getCurrentHIPStream(dev).stream();
+        std::vector<int64_t> vshape = x.sizes().vec(), sshape = vshape;
+        if (fmt == 1) vshape.back() = K / 2;
+        sshape.back() = K / 32;
+        at::Tensor values = at::empty(vshape, x.options().dtype(fmt == 1 ? at::kByte : at::kFloat8_e4m3fn));
+        at::Tensor scales = at::empty(sshape, x.options().dtype(at::kByte));
+        launch_mx_quantize(x.data_ptr(), src_dt, n / 32, fmt, values.data_ptr(),
+                           static_cast<uint8_t*>(scales.data_ptr()), stream);
+        auto wrap = [](at::Tensor t) { return py::reinterpret_steal<py::object>(THPVariable_Wrap(std::move(t))); };
+        return py::make_tuple(wrap(std::move(values)), wrap(std::move(scales)));
+      },
+      py::arg("x"), py::arg("fmt") = 0,
+      "-> (values, scales uint8 [..., K / 32]), launched on the current stream");
+
   // Coalesced variant: when several fixed-width batches are already staged, one allocation and
   // one kernel launch serve up to driver.coalesce of them; the following calls return the
   // pre-collated tensors without any HIP call (MainDriver::step_group_begin/launch).

@@ -37,8 +37,9 @@ import torch
 
 from ..client.errors import CorruptRecordException
 from ..config import LoaderConfig
-from ..ops.collate import (CODE_DTYPE, DTYPE_CODE, FLOAT_DTYPES, BinnedBatch, PackedBatch, _stream_ptr, bin_launch,
-                           normalize_params, pack_launch, pad_bits, reference_binned, reference_packed)
+from ..ops.collate import (CODE_DTYPE, DTYPE_CODE, FLOAT_DTYPES, MX_BLOCK, MX_FORMATS, BinnedBatch, MXBatch,
+                           PackedBatch, _stream_ptr, bin_launch, mx_launch, normalize_params, pack_launch, pad_bits,
+                           reference_binned, reference_mx, reference_packed)
 from ..ops.native import core, hip
 from ..parallel.sharding import dist_rank_world
 from ..utils.metrics import LoaderStats
@@ -65,7 +66,8 @@ def _traced_step(step):
 class KafkaBatch(NamedTuple):
     """Batch plus provenance (``return_info=True``)."""
 
-    data: torch.Tensor    # layout="packed" / "binned": a PackedBatch / BinnedBatch (lengths and mask are then None)
+    data: torch.Tensor    # layout="packed" / "binned": a PackedBatch / BinnedBatch (lengths and mask are then None);
+                          # quantize="mxfp8" / "mxfp4": an MXBatch
     lengths: torch.Tensor | None
     mask: torch.Tensor | None
     watermarks: list      # [(pidx, first_offset, next_offset, n_records)]
@@ -134,6 +136,16 @@ class DeviceLoader(LoaderBridges, LoaderCommits, LoaderLockstep):
             (``row_bin == -1``, counted in ``unplaced``; later rows may still fit).  Such rows, and cut ones, are
             still committed with their batch -- exactly as ``pack_to`` treats an overflow; nothing is carried over
             into the next batch.  At most 16384 rows and bins per batch on the GPU.
+        quantize: ``None`` (default) or ``"mxfp8"`` / ``"mxfp4"``: the batch's values are delivered as a
+            :class:`~torchkafka_amd.MXBatch` in the OCP Microscaling format -- blocks of 32 consecutive elements of
+            the last dimension share one E8M0 scale byte; elements are ``float8_e4m3fn``, or e2m1 codes two per
+            ``uint8`` -- made from the batch ``quantize=None`` would have delivered (same ``dtype``, ``normalize``,
+            padding and ``pad_value``) by one more gfx950 launch (csrc/hip/mx_quant.hip), exactly
+            ``quantize_mx(batch, quantize)``.  ``FixedWidth``: ``x`` becomes the ``MXBatch`` (with record fields
+            ``(MXBatch, key, ...)``) and ``shape[-1]`` must be a multiple of 32; var-len / JSON:
+            ``(MXBatch, lengths[, mask])`` and ``pad_to`` (or, with ``pad_to=None``, ``pad_multiple``) must be a
+            multiple of 32.  The output dtype must be float32, bfloat16 or float16 (``TypeError`` otherwise, and
+            for structured samples); ``layout`` must be ``"padded"``.
         drop_last: drop a final batch shorter than ``batch_size`` (DataLoader's meaning).
         return_info: yield ``(batch, BatchInfo)`` with each batch's partitions and offset ranges.
         native: use the native step driver (``False``: the Python loop, for debugging).
@@ -259,6 +271,9 @@ class DeviceLoader(LoaderBridges, LoaderCommits, LoaderLockstep):
             raise TypeError("layout='binned' needs a VarLen or JsonArray schema (fixed-width and structured "
                             "samples have no row lengths to pack)")
         self._pad_bits: dict = {}
+        self.quantize = cfg.quantize
+        if self.quantize is not None:
+            self._check_quantize()
         self.return_info = cfg.return_info
         self.native = cfg.native
         self.multiprocessing_context = cfg.multiprocessing_context
@@ -353,6 +368,25 @@ class DeviceLoader(LoaderBridges, LoaderCommits, LoaderLockstep):
         if self.event_every is not None:
             return self.event_every
         return max(1, min(4, n_slots // 4))
+
+    def _check_quantize(self) -> None:
+        """``quantize=`` needs a float batch whose last dimension is cut into whole blocks of 32."""
+        s, q = self.schema, self.quantize
+        kind = getattr(s, "kind", None)
+        if kind not in (0, 1, 2):
+            raise TypeError(f"quantize={q!r} needs a FixedWidth, VarLen or JsonArray schema (structured samples "
+                            "have no single values tensor to quantise)")
+        out = self._out_dtype(torch.float32 if kind == 2 else s.dtype)
+        if out not in (torch.float32, torch.bfloat16, torch.float16):
+            raise TypeError(f"quantize={q!r} needs a float32, bfloat16 or float16 batch, not {out} "
+                            "(set dtype=, or use a float schema)")
+        if kind == 0:
+            if not s.shape or s.shape[-1] % MX_BLOCK:
+                raise ValueError(f"quantize={q!r}: the schema's last dimension must be a multiple of {MX_BLOCK}, "
+                                 f"got shape {tuple(s.shape)}")
+        elif (self.pad_to if self.pad_to is not None else self.pad_multiple) % MX_BLOCK:
+            raise ValueError(f"quantize={q!r}: pad_to (or, with pad_to=None, pad_multiple) must be a multiple of "
+                             f"{MX_BLOCK}")
 
     def _default_src_code(self) -> int:
         s = self.schema
@@ -660,7 +694,7 @@ class DeviceLoader(LoaderBridges, LoaderCommits, LoaderLockstep):
                            s.row_elems, shift, scale, native_ac, 100, self.coalesce > 1, nx,
                            self.verify == "deliver")
         if nx < 2 or s.column_order() == list(range(nx)):
-            return drv.fast_next
+            return self._quantized_stage(drv.fast_next)
         order = s.column_order()  # fields added timestamp first: the native columns are key-first
         native = drv.fast_next
 
@@ -668,6 +702,21 @@ class DeviceLoader(LoaderBridges, LoaderCommits, LoaderLockstep):
             r, cs, item = native()
             if item is not None:
                 item = (item[0], *(item[1 + i] for i in order))
+            return r, cs, item
+        return self._quantized_stage(step)
+
+    def _quantized_stage(self, native):
+        """``native`` with the values of every item quantised (``quantize=``), as ``_varlen_stage``
+        wraps ``relayout``: the native step ordered the current stream behind the decode before it
+        handed the batch out, so the quantise kernel goes on that stream right behind it."""
+        if self.quantize is None:
+            return native
+        quantize = self._quantize
+
+        def step():
+            r, cs, item = native()
+            if item is not None:
+                item = (quantize(item[0]), *item[1:]) if isinstance(item, tuple) else quantize(item)
             return r, cs, item
         return step
 
@@ -680,7 +729,7 @@ class DeviceLoader(LoaderBridges, LoaderCommits, LoaderLockstep):
                              self.pad_multiple, float(self.pad_value), bool(self.return_mask), native_ac, 100,
                              self.verify == "deliver")
         if self.layout == "padded":
-            return drv.varlen_fast_next
+            return self._quantized_stage(drv.varlen_fast_next)
         native, relayout = drv.varlen_fast_next, (self._pack if self.layout == "packed" else self._bin)
 
         def step():
@@ -769,6 +818,7 @@ class DeviceLoader(LoaderBridges, LoaderCommits, LoaderLockstep):
             break
         t1 = time.perf_counter_ns()
         if kind == core().PACK_TREE:  # structured samples: one copy of the slot, leaves are views
+            self._refuse_quantized_tree()
             out = self._collate_tree(run, drv.last_slot, payload_bytes,
                                      lambda block: drv.copy_payload_last(_stream_ptr(self.device), block.data_ptr()))
             self.stats.record_batch(n_rows, payload_bytes, t1 - t0, time.perf_counter_ns() - t1)
@@ -795,6 +845,8 @@ class DeviceLoader(LoaderBridges, LoaderCommits, LoaderLockstep):
             ext = torch.empty((nx, n_rows), dtype=torch.int64, device=dev) if nx else None
             drv.collate_fixed_last(stream, DTYPE_CODE[dst_dt], out.data_ptr(), row, shift, scale,
                                    ext.data_ptr() if ext is not None else 0)
+            if self.quantize is not None:
+                out = self._quantize(out)
             if ext is not None and not self.return_info:
                 out = self._with_fields(out, ext)
         else:
@@ -813,6 +865,8 @@ class DeviceLoader(LoaderBridges, LoaderCommits, LoaderLockstep):
                     mask = mask.view(-1)[:n_rows * W].view(n_rows, W)
         if not fixed and self.layout != "padded":
             out, lengths = self._relayout(out, lengths), None
+        elif not fixed and self.quantize is not None:
+            out = self._quantize(out)
         self.stats.record_batch(n_rows, payload_bytes, t1 - t0, time.perf_counter_ns() - t1)
         n_rec = sum(w[3] for w in wms)
         if self.return_info:
@@ -840,6 +894,8 @@ class DeviceLoader(LoaderBridges, LoaderCommits, LoaderLockstep):
     def _collate(self, run: _Run, g: int, summ, wms):
         n_rows, _flags, payload_bytes, voff, max_len, total, _w, kind, src_code = summ
         if kind == core().PACK_TREE:
+            self._refuse_quantized_tree()
+
             def copy(block):
                 run.engine.copy_raw(g, _stream_ptr(self.device), 0, block.data_ptr(), payload_bytes)
             out = self._collate_tree(run, g, payload_bytes, copy)
@@ -915,6 +971,8 @@ class DeviceLoader(LoaderBridges, LoaderCommits, LoaderLockstep):
                 run.ring.main_release(g)
         if not fixed and self.layout != "padded":
             out, lengths = self._relayout(out, lengths), None
+        elif self.quantize is not None:
+            out = self._quantize(out)
         n_rec = sum(w[3] for w in wms)
         if self.return_info:
             return KafkaBatch(out, lengths, mask, wms, n_rec)
@@ -936,6 +994,21 @@ class DeviceLoader(LoaderBridges, LoaderCommits, LoaderLockstep):
         hands it out again only after an event behind this launch; every other route allocates on
         the delivery stream itself, where reuse is ordered behind the launch by the stream."""
         return self._pack(out, lengths) if self.layout == "packed" else self._bin(out, lengths)
+
+    def _quantize(self, out: torch.Tensor) -> MXBatch:
+        """The post-pass of ``quantize=``: a delivered values tensor -> its MXBatch, by one launch on
+        the current stream (csrc/hip/mx_quant.hip; ``reference_mx`` on the CPU).  It sits where
+        ``_relayout`` sits, behind every decode route alike, and the tensor it read is dropped when
+        it returns: safe for the reason ``_relayout`` gives."""
+        if out.device.type != "cuda":
+            return reference_mx(out, self.quantize)
+        if out.numel() >= 1 << 31:
+            raise ValueError(f"quantize={self.quantize!r}: a batch must have fewer than 2^31 elements")
+        return mx_launch(out, MX_FORMATS[self.quantize], self.quantize)
+
+    def _refuse_quantized_tree(self) -> None:
+        if self.quantize is not None:
+            raise TypeError(f"quantize={self.quantize!r}: structured samples have no single values tensor to quantise")
 
     def _bin(self, out: torch.Tensor, lengths: torch.Tensor) -> BinnedBatch:
         """A delivered padded batch -> its BinnedBatch (two launches, csrc/hip/bin.hip)."""

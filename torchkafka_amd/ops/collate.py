@@ -263,7 +263,135 @@ def bin_padded(padded: torch.Tensor, lengths: torch.Tensor, seq_len: int, bins: 
     return bin_launch(padded.contiguous(), lengths, seq_len, bins, pad_bits(padded.dtype, pad_value))
 
 
+# ----------------------------------------------------------------------------- MX block-scaled formats
+MX_FORMATS = {"mxfp8": 0, "mxfp4": 1}   # name -> the kernel's format code
+_MX_EMAX_TOP = {"mxfp8": (8, 448.0), "mxfp4": (2, 6.0)}
+_MX_SOURCES = (torch.float32, torch.bfloat16, torch.float16)
+MX_BLOCK = 32
+_E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+def _exp2i(e: torch.Tensor) -> torch.Tensor:
+    """``2.0 ** e`` as exact f32 for an integer tensor ``e`` in [-126, 127], built from its bits."""
+    return ((e.to(torch.int32) + 127) << 23).view(torch.float32)
+
+
+class MXBatch(NamedTuple):
+    """A tensor in an OCP Microscaling (MX v1.0) format: blocks of 32 consecutive elements of the last
+    dimension share one power-of-two scale (``quantize_mx``, ``DeviceLoader(quantize=...)``).
+
+    Fields:
+        values: ``"mxfp8"``: ``float8_e4m3fn`` in the input's shape.  ``"mxfp4"``: ``uint8`` with the last
+            dimension halved, two e2m1 codes per byte -- element ``2i`` in the low nibble, ``2i + 1`` in
+            the high one (torch's ``float4_e2m1fn_x2`` convention); a code is ``sign << 3 | index`` into
+            the magnitudes 0, .5, 1, 1.5, 2, 3, 4, 6.
+        scales: ``uint8`` E8M0 bytes in the input's shape with the last dimension ``/ 32``, plain
+            row-major: block ``b`` of a row stands for ``2 ** (scales[..., b] - 127)`` times its elements;
+            0xFF marks a block that held a NaN or an infinity (it dequantises to NaN, its element bytes
+            are 0).  The pre-swizzled scale layouts that particular GEMM libraries want are out of
+            scope: permute ``scales`` yourself.
+        fmt: ``"mxfp8"`` or ``"mxfp4"``.
+    """
+
+    values: torch.Tensor
+    scales: torch.Tensor
+    fmt: str
+
+    @property
+    def scales_e8m0(self) -> torch.Tensor:
+        """``scales`` viewed as ``torch.float8_e8m0fnu`` (no copy)."""
+        return self.scales.view(torch.float8_e8m0fnu)
+
+    @property
+    def values_fp4x2(self) -> torch.Tensor:
+        """mxfp4 ``values`` viewed as ``torch.float4_e2m1fn_x2`` (no copy)."""
+        if self.fmt != "mxfp4":
+            raise TypeError(f"values_fp4x2: the batch is {self.fmt}, not mxfp4")
+        return self.values.view(torch.float4_e2m1fn_x2)
+
+    def dequantize(self, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+        """The values the batch stands for, in the input's shape: plain torch on the batch's device,
+        integer arithmetic on the scale bytes and exact power-of-two scaling (no arithmetic on
+        ``float8_e8m0fnu`` / ``float4_e2m1fn_x2`` tensors)."""
+        if self.fmt == "mxfp8":
+            v = self.values.to(torch.float32)
+        else:
+            lut = torch.tensor(_E2M1 + tuple(-m for m in _E2M1), dtype=torch.float32, device=self.values.device)
+            codes = torch.stack([self.values & 0xF, self.values >> 4], dim=-1)
+            v = lut[codes.to(torch.int64)].flatten(-2)
+        shape = v.shape
+        e = self.scales.to(torch.int32) - 127                    # [-127, 127]; 128: the NaN scale
+        nan = (e == 128).unsqueeze(-1)
+        e = e.clamp(max=127)
+        lo = e >> 1                                              # 2^e = 2^lo * 2^(e - lo), both factors normal
+        v = v.reshape(*self.scales.shape, MX_BLOCK) * _exp2i(lo).unsqueeze(-1) * _exp2i(e - lo).unsqueeze(-1)
+        v = torch.where(nan, torch.full_like(v, float("nan")), v)
+        return v.reshape(shape).to(dtype)
+
+
+def _mx_check(x: torch.Tensor, fmt: str) -> None:
+    if fmt not in MX_FORMATS:
+        raise ValueError(f"mx: fmt must be 'mxfp8' or 'mxfp4', not {fmt!r}")
+    if not isinstance(x, torch.Tensor) or x.dtype not in _MX_SOURCES:
+        got = x.dtype if isinstance(x, torch.Tensor) else type(x).__name__
+        raise TypeError(f"mx: the input must be a float32, bfloat16 or float16 tensor, not {got}")
+    if x.dim() < 1 or x.shape[-1] % MX_BLOCK:
+        raise ValueError(f"mx: the last dimension must be a multiple of {MX_BLOCK}, got shape {tuple(x.shape)}")
+    if x.numel() >= _PACK_LIMIT:
+        raise ValueError("mx: numel must be below 2^31")
+
+
+def mx_launch(x: torch.Tensor, code: int, fmt: str) -> MXBatch:
+    """The quantise kernel on the current stream; ``x`` contiguous f32 / bf16 / f16 on the GPU with
+    ``shape[-1] % 32 == 0`` (the loader's per-batch entry: no checks).  The kernel loads 16 bytes per
+    lane: a view that starts off a 16-byte boundary is copied first."""
+    if x.data_ptr() % 16:
+        x = x.clone()
+    values, scales = hip().mx_tensors(x, code)  # allocates the outputs natively
+    return MXBatch(values, scales, fmt)
+
+
+def quantize_mx(x: torch.Tensor, fmt: str = "mxfp8") -> MXBatch:
+    """``x`` (float32, bfloat16 or float16; last dimension a multiple of 32; ``numel < 2^31``) ->
+    :class:`MXBatch`, in one gfx950 launch on the current stream (csrc/hip/mx_quant.hip).  Per block
+    of 32: the scale is ``2 ** (floor(log2(amax)) - emax)`` (emax 8 / 2, the exponent clamped to
+    [-127, 127]), each element is ``x / scale`` saturated to +-448 / +-6 and rounded to nearest even;
+    a block with a NaN or an infinity gets the NaN scale 0xFF and zero elements.  A non-contiguous
+    input is made contiguous.  CPU tensors take :func:`reference_mx`."""
+    _mx_check(x, fmt)
+    if x.device.type != "cuda":
+        return reference_mx(x, fmt)
+    return mx_launch(x.contiguous(), MX_FORMATS[fmt], fmt)
+
+
 # ----------------------------------------------------------------------------- torch references
+def reference_mx(x: torch.Tensor, fmt: str = "mxfp8") -> MXBatch:
+    """:func:`quantize_mx` in plain torch, on any device (the CPU path), byte for byte."""
+    _mx_check(x, fmt)
+    emax, top = _MX_EMAX_TOP[fmt]
+    K = x.shape[-1]
+    blk = x.contiguous().to(torch.float32).reshape(-1, MX_BLOCK)  # bf16 / f16 widen exactly
+    mag = blk.view(torch.int32) & 0x7FFFFFFF
+    amax = mag.max(dim=1).values if blk.shape[0] else mag.new_zeros(0)  # orders |v|; NaN and Inf on top
+    bad = amax >= 0x7F800000
+    se = ((amax >> 23) - 127 - emax).clamp(min=-127)             # a zero or subnormal amax: field 0, clamps
+    # ldexp(v, -se) as one exact multiply: 2^-se is a normal f32 for every -se in [-125, 127]
+    y = (blk * _exp2i(-se).unsqueeze(1)).clamp(-top, top)
+    y = torch.where(bad.unsqueeze(1), torch.zeros_like(y), y)    # (keeps NaN out of the encoders)
+    if fmt == "mxfp8":
+        codes = y.to(torch.float8_e4m3fn).view(torch.uint8)
+    else:
+        a = y.abs()
+        idx = ((a > 0.25).to(torch.uint8) + (a >= 0.75) + (a > 1.25) + (a >= 1.75) + (a > 2.5) + (a >= 3.5) + (a > 5.0))
+        codes = idx | (torch.signbit(y).to(torch.uint8) << 3)    # midpoints went to the even index above
+    codes = torch.where(bad.unsqueeze(1), torch.zeros_like(codes), codes)
+    scales = torch.where(bad, torch.full_like(se, 255), se + 127).to(torch.uint8).reshape(*x.shape[:-1], K // MX_BLOCK)
+    if fmt == "mxfp8":
+        return MXBatch(codes.view(torch.float8_e4m3fn).reshape(x.shape), scales, fmt)
+    pairs = codes.reshape(-1, 2)
+    return MXBatch((pairs[:, 0] | (pairs[:, 1] << 4)).reshape(*x.shape[:-1], K // 2), scales, fmt)
+
+
 def reference_fixed(src: torch.Tensor, dtype: torch.dtype, normalize=None) -> torch.Tensor:
     if normalize is None:
         return src.to(dtype)
