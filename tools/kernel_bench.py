@@ -14,7 +14,10 @@ beside: a boolean-mask gather synchronises with the host, so it cannot be graph-
 ``mx_quantize`` (f32 / bf16 -> OCP MX blocks, mx_quant.hip) stands beside ``reference_mx``, the
 plain-torch composition of the same rules, running on the same GPU; the two are timed alternately.
 
-Usage: python tools/kernel_bench.py [--quick] [--iters N] [--only pack_rows|mx_quantize]
+``struct_split`` (packed struct records -> one tensor per field, struct_split.hip) stands beside
+``reference_struct``, the slice / view / to composition in plain torch, on the same device tensors.
+
+Usage: python tools/kernel_bench.py [--quick] [--iters N] [--only pack_rows|mx_quantize|struct_split]
 """
 import argparse
 import json
@@ -174,11 +177,79 @@ def mx_quantize_cases(dev, iters, rounds=3):
     return res
 
 
+def struct_split_cases(dev, iters, rounds=3):
+    """Three struct batches -> their field tensors by one launch (struct_split.hip): the README
+    struct (256 x 308 B, five fields), 256 x 1 KiB with four fields, 4096 x 64 B with eight scalar
+    fields.  ``gpu_us``: device time per launch (graph replay); ``GBps``: (record bytes read + field
+    bytes written) / time and its share of the measured HBM roof; ``torch_gpu_us``:
+    ``reference_struct`` on the same device tensors -- the slice / view / to composition a user would
+    write -- graph-replayed too, the two alternated ``rounds`` times (median reported, spread kept);
+    ``eager_us`` / ``torch_eager_us``: wall time per call with the host's launch cost."""
+    import statistics
+
+    import torch
+
+    from torchkafka_amd import Field, Struct
+    from torchkafka_amd.ops.collate import reference_struct, split_struct, struct_launch
+    from torchkafka_amd.ops.native import hip
+
+    mod = hip()
+    f32, f16, bf16 = torch.float32, torch.float16, torch.bfloat16
+    u8, i8, i32, i64 = torch.uint8, torch.int8, torch.int32, torch.int64
+    readme = Struct(Field("flag", u8), Field("features", f32, (64,), out=bf16, normalize=(0.5, 2.0)),
+                    Field("ids", i32, (2, 4), out=i64), Field("weight", f16), Field("label", i64, offset=300), size=308)
+    kib = Struct(Field("dense", f32, (192,), out=bf16, normalize=(0.0, 1.5)), Field("ids", i32, (48,), out=i64),
+                 Field("weight", f32, offset=1012), Field("label", i64, offset=1016), size=1024)
+    scalars = Struct(Field("a", f32), Field("b", f32, out=bf16), Field("c", i64), Field("d", i32, out=i64),
+                     Field("e", f16, out=f32), Field("f", u8), Field("g", i8, out=i32, offset=27),
+                     Field("h", bf16, offset=29), size=64)
+    g = torch.Generator().manual_seed(3)
+    res = []
+    for name, schema, rows in (("README struct 256 x 308 B, 5 fields", readme, 256),
+                               ("256 x 1 KiB, 4 fields", kib, 256),
+                               ("4096 x 64 B, 8 scalar fields", scalars, 4096)):
+        raw = torch.randint(0, 120, (rows, schema.size), dtype=u8, generator=g).to(dev)  # bytes < 0x78: no NaN
+        ours, ref = split_struct(raw, schema), reference_struct(raw, schema)
+        for f in schema.members:
+            a, b = ours[f.name], ref[f.name]
+            assert a.dtype == b.dtype and torch.equal(a.view(torch.uint8), b.contiguous().view(torch.uint8)), f.name
+        nbytes = raw.numel() + sum(t.numel() * t.element_size() for t in ours.values())
+        outs = [torch.empty_like(ours[f.name]) for f in schema.members]
+        spec = schema.device_spec(raw.device)
+        table = [(off, f.elems, src, dst, o.data_ptr(), shift, scale)
+                 for (off, _s, src, dst, shift, scale), f, o in zip(spec, schema.members, outs)]
+
+        def kernel():
+            mod.struct_split(raw.data_ptr(), rows, schema.size, table, torch.cuda.current_stream(dev).cuda_stream)
+
+        kernel()
+        for f, o in zip(schema.members, outs):
+            assert torch.equal(o.view(torch.uint8), ours[f.name].view(torch.uint8)), f.name
+        t_ours, t_ref = [], []
+        for _ in range(rounds):  # alternated: other work shares the machine
+            t_ours.append(timeit_graph(kernel, iters))
+            t_ref.append(timeit_graph(lambda: reference_struct(raw, schema), iters))
+        g_ours, g_ref = statistics.median(t_ours), statistics.median(t_ref)
+        e_ours = timeit(lambda: split_struct(raw, schema), iters)
+        e_ref = timeit(lambda: reference_struct(raw, schema), iters)
+        t_entry = timeit(lambda: struct_launch(raw, schema), iters)  # what the loader calls per batch
+        res.append({"kernel": "struct_split", "case": name, "gpu_us": round(g_ours, 2),
+                    "gpu_us_rounds": [round(t, 2) for t in t_ours], "bytes": nbytes,
+                    "tile_rows": int(mod.struct_tile_rows(rows, schema.size)),
+                    "GBps": round(nbytes / g_ours / 1e3, 1),
+                    "hbm_roof_share": round(nbytes / g_ours / 1e3 / HBM_ROOF_GBPS, 4),
+                    "torch_gpu_us": round(g_ref, 2), "torch_gpu_us_rounds": [round(t, 2) for t in t_ref],
+                    "eager_us": round(e_ours, 2), "torch_eager_us": round(e_ref, 2),
+                    "loader_entry_us": round(t_entry, 2)})
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true", help="fewer iterations (for counter collection)")
     ap.add_argument("--iters", type=int, default=200)
-    ap.add_argument("--only", default=None, choices=["pack_rows", "mx_quantize"], help="run only this kernel's cases")
+    ap.add_argument("--only", default=None, choices=["pack_rows", "mx_quantize", "struct_split"],
+                    help="run only this kernel's cases")
     args = ap.parse_args()
     iters = 20 if args.quick else args.iters
 
@@ -195,6 +266,10 @@ def main():
         return
     if args.only == "mx_quantize":
         for r in mx_quantize_cases(dev, iters):
+            print(json.dumps(r))
+        return
+    if args.only == "struct_split":
+        for r in struct_split_cases(dev, iters):
             print(json.dumps(r))
         return
     out = []
@@ -322,6 +397,7 @@ def main():
 
     out += pack_rows_cases(dev, iters)
     out += mx_quantize_cases(dev, iters)
+    out += struct_split_cases(dev, iters)
     for r in out:
         print(json.dumps(r))
 

@@ -9,9 +9,9 @@ import numpy.random  # noqa: F401  -- import eagerly: a lazy import racing a Dat
 
 from .config import LoaderConfig, Tuning
 from .loader import DeviceLoader, KafkaBatch, auto_commit
-from .models import FixedWidth, JsonArray, KafkaDataset, Key, Timestamp, VarLen, WithFields
+from .models import Field, FixedWidth, JsonArray, KafkaDataset, Key, Struct, Timestamp, VarLen, WithFields
 from .ops.collate import (BinnedBatch, MXBatch, PackedBatch, bin_padded, pack_padded, quantize_mx, reference_binned,
-                          reference_mx, reference_packed)
+                          reference_mx, reference_packed, reference_struct, split_struct)
 
 __version__ = "1.2.0+mi355x.7"
 
@@ -19,7 +19,7 @@ __all__ = ["KafkaDataset", "auto_commit", "DeviceLoader", "KafkaBatch", "PackedB
            "Tuning", "FixedWidth", "VarLen", "JsonArray", "Key", "Timestamp", "WithFields", "SyntheticBroker",
            "KafkaBridge", "KafkaWireServer", "KafkaConsumer", "KafkaProducer", "TopicPartition",
            "ConsumerRebalanceListener", "pack_padded", "reference_packed", "bin_padded", "reference_binned", "MXBatch",
-           "quantize_mx", "reference_mx"]
+           "quantize_mx", "reference_mx", "Struct", "Field", "split_struct", "reference_struct"]
 
 
 def __getattr__(name):

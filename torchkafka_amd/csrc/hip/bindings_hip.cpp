@@ -183,6 +183,33 @@ PYBIND11_MODULE(_tkhip, m) {
       py::arg("src"), py::arg("src_dtype"), py::arg("n_blocks"), py::arg("fmt"), py::arg("values"), py::arg("scales"),
       py::arg("stream") = 0);
 
+  m.attr("STRUCT_MAX_FIELDS") = kStructMaxFields;
+  m.attr("STRUCT_MAX_RECORD") = kStructMaxRecord;
+  m.attr("STRUCT_COPY") = kStructCopy;
+  m.def("struct_tile_rows", [](int64_t rows, int32_t record_bytes) {
+    if (record_bytes < 4) throw std::invalid_argument("struct_tile_rows: record_bytes must be at least 4");
+    return struct_tile_rows(rows, record_bytes);
+  }, py::arg("rows"), py::arg("record_bytes"), "rows of one workgroup's tile");
+  m.def(
+      "struct_split",
+      [](uintptr_t raw, int64_t rows, int32_t record_bytes, const std::vector<py::tuple>& table, uintptr_t stream) {
+        if (table.size() > size_t(kStructMaxFields))
+          throw std::invalid_argument("struct split: at most " + std::to_string(kStructMaxFields) + " fields");
+        StructTable t{};
+        t.n = int32_t(table.size());
+        for (size_t i = 0; i < table.size(); ++i) {
+          const py::tuple& e = table[i];
+          if (e.size() != 7)
+            throw std::invalid_argument("struct split: an entry is (src_off, elems, src_dt, dst_dt, dst, shift, scale)");
+          t.f[i] = StructField{e[0].cast<int32_t>(), e[1].cast<int32_t>(), e[2].cast<int32_t>(), e[3].cast<int32_t>(),
+                               ptr<void>(e[4].cast<uintptr_t>()), ptr<const float>(e[5].cast<uintptr_t>()),
+                               ptr<const float>(e[6].cast<uintptr_t>())};
+        }
+        launch_struct_split(ptr<const void>(raw), rows, record_bytes, t, stream_of(stream));
+      },
+      py::arg("raw"), py::arg("rows"), py::arg("record_bytes"), py::arg("table"), py::arg("stream") = 0,
+      "table: up to STRUCT_MAX_FIELDS entries (src_off, elems, src_dtype, dst_dtype | STRUCT_COPY, dst, shift, scale)");
+
   m.def(
       "launch_json_rows",
       [](uintptr_t rows, uintptr_t vals, uintptr_t out, int dst_dt, int64_t n_rows, int64_t L, double pad,

@@ -108,6 +108,33 @@ constexpr int kMxMaxGrid = 2048;
 void launch_mx_quantize(const void* src, int src_dt, int64_t n_blocks, int fmt, void* values, uint8_t* scales,
                         hipStream_t stream);
 
+// Packed little-endian struct records raw[rows, record_bytes] (4-byte aligned) -> one dense tensor
+// per field (struct_split.hip).  Field f is `elems` elements of `src_dt` at byte `src_off` of every
+// record -- any byte offset; fields may leave gaps and may overlap -- and is written to
+// dst[rows, elems] (aligned to its element size) as `dst_dt`: kStructCopy copies the bytes in the
+// field's own dtype, f32 / f16 / bf16 / fp8 / i32 / i64 convert by convert.h (a float field has float
+// destinations only).  shift / scale: device f32[elems], both or neither; float destinations only.
+// The table travels by value in the kernel arguments; one launch for all fields.
+constexpr int kStructMaxFields = 32;
+constexpr int kStructMaxRecord = 32768;
+constexpr int kStructCopy = -1;
+struct StructField {
+  int32_t src_off, elems;
+  int32_t src_dt, dst_dt;
+  void* dst;
+  const float* shift;
+  const float* scale;
+};
+struct StructTable {
+  int32_t n;
+  StructField f[kStructMaxFields];
+};
+// rows of a workgroup's tile: at most 64 and at most 32 KiB, halved down to 16 while the batch has
+// fewer than 64 tiles
+int struct_tile_rows(int64_t rows, int32_t record_bytes);
+void launch_struct_split(const void* raw, int64_t rows, int32_t record_bytes, const StructTable& table,
+                         hipStream_t stream);
+
 std::vector<std::pair<std::string, double>> api_bench(int device, int iters);
 
 }  // namespace tkh

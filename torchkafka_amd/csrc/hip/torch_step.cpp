@@ -753,6 +753,58 @@ void register_torch_step(py::module_& m) {
       py::arg("x"), py::arg("fmt") = 0,
       "-> (values, scales uint8 [..., K / 32]), launched on the current stream");
 
+  // A batch of packed struct records -> one tensor per field (struct_split.hip), outputs allocated
+  // here on the current stream, as mx_tensors does.  `raw`: contiguous int32 [rows, record_bytes / 4]
+  // or uint8 [rows, record_bytes]; `fields`: (src_off, shape, src_dtype, dst_dtype | STRUCT_COPY,
+  // shift, scale) with shift / scale the addresses of device f32[prod(shape)] vectors, or 0.
+  m.def(
+      "struct_tensors",
+      [](py::handle raw_h, int32_t record_bytes, const std::vector<py::tuple>& fields) -> py::list {
+        if (!THPVariable_Check(raw_h.ptr())) throw std::invalid_argument("struct_tensors: raw must be a tensor");
+        const at::Tensor& raw = THPVariable_Unpack(raw_h.ptr());
+        if (!raw.is_cuda() || raw.dim() != 2 || !raw.is_contiguous() ||
+            (raw.scalar_type() != at::kInt && raw.scalar_type() != at::kByte) ||
+            raw.size(1) * int64_t(raw.element_size()) != record_bytes)
+          throw std::invalid_argument("struct_tensors: raw must be a contiguous device tensor, int32 "
+                                      "[rows, record_bytes / 4] or uint8 [rows, record_bytes]");
+        if (fields.size() > size_t(kStructMaxFields))
+          throw std::invalid_argument("struct_tensors: at most " + std::to_string(kStructMaxFields) + " fields");
+        const int64_t rows = raw.size(0);
+        const auto dev = raw.device().index();
+        hipStream_t stream = c10::hip::getCurrentHIPStream(dev).stream();
+        StructTable t{};
+        t.n = int32_t(fields.size());
+        py::list out;
+        std::vector<int64_t> shape;
+        for (size_t i = 0; i < fields.size(); ++i) {
+          const py::tuple& e = fields[i];
+          if (e.size() != 6)
+            throw std::invalid_argument("struct_tensors: a field is (src_off, shape, src_dt, dst_dt, shift, scale)");
+          StructField& f = t.f[i];
+          f.src_off = e[0].cast<int32_t>();
+          f.src_dt = e[2].cast<int32_t>();
+          f.dst_dt = e[3].cast<int32_t>();
+          f.shift = reinterpret_cast<const float*>(e[4].cast<uintptr_t>());
+          f.scale = reinterpret_cast<const float*>(e[5].cast<uintptr_t>());
+          shape.assign(1, rows);
+          int64_t elems = 1;
+          for (py::handle d : e[1]) {
+            shape.push_back(d.cast<int64_t>());
+            if (shape.back() < 1 || (elems *= shape.back()) > kStructMaxRecord)
+              throw std::invalid_argument("struct_tensors: a field's shape does not fit a record");
+          }
+          f.elems = int32_t(elems);
+          at::Tensor o = at::empty(shape, raw.options().dtype(scalar_type_of(f.dst_dt == kStructCopy ? f.src_dt
+                                                                                                      : f.dst_dt)));
+          f.dst = o.data_ptr();
+          out.append(py::reinterpret_steal<py::object>(THPVariable_Wrap(std::move(o))));
+        }
+        launch_struct_split(raw.data_ptr(), rows, record_bytes, t, stream);
+        return out;
+      },
+      py::arg("raw"), py::arg("record_bytes"), py::arg("fields"),
+      "-> [tensor [rows, *shape] per field], one launch on the current stream");
+
   // Coalesced variant: when several fixed-width batches are already staged, one allocation and
   // one kernel launch serve up to driver.coalesce of them; the following calls return the
   // pre-collated tensors without any HIP call (MainDriver::step_group_begin/launch).

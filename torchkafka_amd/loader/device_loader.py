@@ -37,9 +37,11 @@ import torch
 
 from ..client.errors import CorruptRecordException
 from ..config import LoaderConfig
+from ..models.schema import Struct
 from ..ops.collate import (CODE_DTYPE, DTYPE_CODE, FLOAT_DTYPES, MX_BLOCK, MX_FORMATS, BinnedBatch, MXBatch,
                            PackedBatch, _stream_ptr, bin_launch, mx_launch, normalize_params, pack_launch, pad_bits,
-                           reference_binned, reference_mx, reference_packed)
+                           reference_binned, reference_mx, reference_packed, reference_struct, split_struct,
+                           struct_launch)
 from ..ops.native import core, hip
 from ..parallel.sharding import dist_rank_world
 from ..utils.metrics import LoaderStats
@@ -67,7 +69,7 @@ class KafkaBatch(NamedTuple):
     """Batch plus provenance (``return_info=True``)."""
 
     data: torch.Tensor    # layout="packed" / "binned": a PackedBatch / BinnedBatch (lengths and mask are then None);
-                          # quantize="mxfp8" / "mxfp4": an MXBatch
+                          # quantize="mxfp8" / "mxfp4": an MXBatch; a Struct schema: the dict of field tensors
     lengths: torch.Tensor | None
     mask: torch.Tensor | None
     watermarks: list      # [(pidx, first_offset, next_offset, n_records)]
@@ -271,6 +273,11 @@ class DeviceLoader(LoaderBridges, LoaderCommits, LoaderLockstep):
             raise TypeError("layout='binned' needs a VarLen or JsonArray schema (fixed-width and structured "
                             "samples have no row lengths to pack)")
         self._pad_bits: dict = {}
+        # a Struct schema rides as its int32 carrier and is split behind the decode (_split); a dataset
+        # with a _process of its own takes the per-record path, where the schema is not used
+        self._struct = self.schema if isinstance(self.schema, Struct) and not self._process_overridden() else None
+        if isinstance(self.schema, Struct):
+            self._check_struct()
         self.quantize = cfg.quantize
         if self.quantize is not None:
             self._check_quantize()
@@ -368,6 +375,17 @@ class DeviceLoader(LoaderBridges, LoaderCommits, LoaderLockstep):
         if self.event_every is not None:
             return self.event_every
         return max(1, min(4, n_slots // 4))
+
+    def _check_struct(self) -> None:
+        """A Struct schema converts per field: the loader-wide conversions do not apply to it."""
+        if self.dtype is not None or self.normalize is not None:
+            raise TypeError("a Struct schema takes no loader dtype= / normalize=: set out= / normalize= on its fields")
+        if self.config.quantize is not None:
+            raise TypeError(f"quantize={self.config.quantize!r}: a Struct batch is a dict of field tensors, not one "
+                            "values tensor to quantise")
+        if self.layout != "padded":
+            raise TypeError(f"layout={self.layout!r} needs a VarLen or JsonArray schema (a Struct batch is a dict of "
+                            "fixed-shape field tensors)")
 
     def _check_quantize(self) -> None:
         """``quantize=`` needs a float batch whose last dimension is cut into whole blocks of 32."""
@@ -694,7 +712,7 @@ class DeviceLoader(LoaderBridges, LoaderCommits, LoaderLockstep):
                            s.row_elems, shift, scale, native_ac, 100, self.coalesce > 1, nx,
                            self.verify == "deliver")
         if nx < 2 or s.column_order() == list(range(nx)):
-            return self._quantized_stage(drv.fast_next)
+            return self._struct_stage(self._quantized_stage(drv.fast_next))
         order = s.column_order()  # fields added timestamp first: the native columns are key-first
         native = drv.fast_next
 
@@ -717,6 +735,21 @@ class DeviceLoader(LoaderBridges, LoaderCommits, LoaderLockstep):
             r, cs, item = native()
             if item is not None:
                 item = (quantize(item[0]), *item[1:]) if isinstance(item, tuple) else quantize(item)
+            return r, cs, item
+        return step
+
+    def _struct_stage(self, native):
+        """``native`` with every item -- the int32 carrier batch of a ``Struct`` schema -- split into
+        its dict of field tensors, as ``_quantized_stage`` wraps ``_quantize``: the split kernel goes
+        on the current stream right behind the decode the native step ordered it after."""
+        if self._struct is None:
+            return native
+        split = self._split
+
+        def step():
+            r, cs, item = native()
+            if item is not None:
+                item = split(item)
             return r, cs, item
         return step
 
@@ -847,6 +880,8 @@ class DeviceLoader(LoaderBridges, LoaderCommits, LoaderLockstep):
                                    ext.data_ptr() if ext is not None else 0)
             if self.quantize is not None:
                 out = self._quantize(out)
+            elif self._struct is not None:
+                out = self._split(out)
             if ext is not None and not self.return_info:
                 out = self._with_fields(out, ext)
         else:
@@ -973,6 +1008,8 @@ class DeviceLoader(LoaderBridges, LoaderCommits, LoaderLockstep):
             out, lengths = self._relayout(out, lengths), None
         elif self.quantize is not None:
             out = self._quantize(out)
+        elif fixed and self._struct is not None:
+            out = self._split(out)
         n_rec = sum(w[3] for w in wms)
         if self.return_info:
             return KafkaBatch(out, lengths, mask, wms, n_rec)
@@ -1005,6 +1042,18 @@ class DeviceLoader(LoaderBridges, LoaderCommits, LoaderLockstep):
         if out.numel() >= 1 << 31:
             raise ValueError(f"quantize={self.quantize!r}: a batch must have fewer than 2^31 elements")
         return mx_launch(out, MX_FORMATS[self.quantize], self.quantize)
+
+    def _split(self, out: torch.Tensor) -> dict:
+        """The post-pass of a ``Struct`` schema: the delivered int32 carrier batch ``[rows, size / 4]``
+        -> the dict of field tensors, by one launch on the current stream whatever the number of
+        fields (csrc/hip/struct_split.hip; ``reference_struct`` on the CPU).  It sits where
+        ``_relayout`` and ``_quantize`` sit, behind every decode route alike, and the carrier batch is
+        dropped when it returns: safe for the reason ``_relayout`` gives."""
+        if out.device.type != "cuda":
+            return reference_struct(out, self._struct)
+        if out.shape[0] == 0 or out.numel() * 4 >= 1 << 31:
+            return split_struct(out, self._struct)  # no launch / the ValueError that names the limit
+        return struct_launch(out, self._struct)
 
     def _refuse_quantized_tree(self) -> None:
         if self.quantize is not None:

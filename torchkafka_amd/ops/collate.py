@@ -364,7 +364,61 @@ def quantize_mx(x: torch.Tensor, fmt: str = "mxfp8") -> MXBatch:
     return mx_launch(x.contiguous(), MX_FORMATS[fmt], fmt)
 
 
+# ----------------------------------------------------------------------------- struct records
+def _struct_check(raw: torch.Tensor, schema) -> torch.Tensor:
+    size = schema.size
+    if not isinstance(raw, torch.Tensor) or raw.dim() != 2 or not (
+            (raw.dtype == torch.int32 and raw.shape[1] * 4 == size) or
+            (raw.dtype == torch.uint8 and raw.shape[1] == size)):
+        got = (raw.dtype, tuple(raw.shape)) if isinstance(raw, torch.Tensor) else type(raw).__name__
+        raise ValueError(f"struct: raw must be int32 [rows, {size // 4}] or uint8 [rows, {size}], got {got}")
+    if not raw.is_contiguous():
+        raise ValueError("struct: raw must be contiguous")
+    if raw.shape[0] * size >= _PACK_LIMIT:
+        raise ValueError("struct: rows * size must be below 2^31")
+    return raw
+
+
+def struct_launch(raw: torch.Tensor, schema) -> dict:
+    """The split kernel on the current stream; ``raw`` a contiguous device batch of ``schema``'s
+    carrier with at least one row (the loader's per-batch entry: no checks).  The kernel reads
+    dwords: a view that starts off a 4-byte boundary is copied first."""
+    if raw.data_ptr() % 4:
+        raw = raw.clone()
+    outs = hip().struct_tensors(raw, schema.size, schema.device_spec(raw.device))  # allocates the outputs natively
+    return {f.name: t for f, t in zip(schema.members, outs)}
+
+
+def split_struct(raw: torch.Tensor, schema) -> dict:
+    """A batch of :class:`~torchkafka_amd.Struct` records -- contiguous int32 ``[rows, size // 4]``
+    (the delivered carrier) or uint8 ``[rows, size]`` -- -> ``{field name: tensor [rows, *shape]}``
+    with every field's ``out`` and ``normalize`` applied, in one gfx950 launch on the current stream
+    (csrc/hip/struct_split.hip) whatever the number of fields.  ``rows == 0`` makes no launch.  CPU
+    tensors take :func:`reference_struct`."""
+    _struct_check(raw, schema)
+    if raw.device.type != "cuda":
+        return reference_struct(raw, schema)
+    if raw.shape[0] == 0:
+        return {f.name: torch.empty((0, *f.shape), dtype=f.out_dtype, device=raw.device) for f in schema.members}
+    return struct_launch(raw, schema)
+
+
 # ----------------------------------------------------------------------------- torch references
+def reference_struct(raw: torch.Tensor, schema) -> dict:
+    """:func:`split_struct` in plain torch, on any device (the CPU loader's path), bit for bit: per
+    field a copy of its byte slice viewed as ``dtype``, ``.to(out)`` and the normalise step."""
+    _struct_check(raw, schema)
+    rows = raw.shape[0]
+    by = raw.view(torch.uint8)
+    out = {}
+    for f, off in zip(schema.members, schema.offsets):
+        # a fresh dense copy, not contiguous(): a one-row slice already counts as contiguous and would
+        # keep its odd offset and the record's stride
+        x = by[:, off:off + f.nbytes].clone(memory_format=torch.contiguous_format).view(f.dtype).view(rows, *f.shape)
+        out[f.name] = f.convert(x)
+    return out
+
+
 def reference_mx(x: torch.Tensor, fmt: str = "mxfp8") -> MXBatch:
     """:func:`quantize_mx` in plain torch, on any device (the CPU path), byte for byte."""
     _mx_check(x, fmt)
